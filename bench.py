@@ -12,6 +12,18 @@ Single GPU:   python bench.py --gpus 1 --steps 20 --warmup 5
 Multi-GPU (driver does this):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times ``--steps`` train iterations and prints
+one JSON result line.  ``--dump-outputs DIR`` additionally writes what the
+last timed ``run_train_iter`` returned (``loss``, ``accuracy`` and the
+per-task target logits) as float32 ``DIR/<name>.npy``; model init and the
+synthetic episodes are seeded, so equal arguments give equal inputs.  A dump
+run also turns on the deterministic-reduction mode (MAML355_DETERMINISTIC=1,
+unless that variable is already set), because with atomic reductions the
+random-pixel workload does not repeat from run to run; its result line says
+``"deterministic_reductions": true`` and its throughput is that mode's.
+``--full`` is reserved for measurements beyond the headline figure; the
+benchmark has none today, so it changes nothing yet.
 """
 
 from __future__ import annotations
@@ -39,7 +51,32 @@ def parse_cli():
     p.add_argument("--model", type=str, default="maml++_miniimagenet_5w1s",
                    choices=["maml++_miniimagenet_5w1s", "maml++_omniglot_20w5s"])
     p.add_argument("--second_order", type=str, default="True")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run measurements beyond the headline figure "
+                        "(none exist yet)")
+    cli = p.parse_args()
+    if cli.dump_outputs is not None and cli.steps < 1:
+        p.error("--dump-outputs needs at least one timed step")
+    return cli
+
+
+def dump_outputs(out_dir: str, rank: int, losses, per_task_preds) -> None:
+    """Write what the last timed ``run_train_iter`` returned, as float32
+    arrays (a few hundred KB at the default meta-batch).  Rank 0 writes
+    ``<name>.npy``; further ranks hold other tasks and write
+    ``<name>.rank<r>.npy``."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    arrays = {
+        "loss": np.asarray([losses["loss"]], dtype=np.float32),
+        "accuracy": np.asarray([losses["accuracy"]], dtype=np.float32),
+        "per_task_logits": per_task_preds.float().cpu().numpy(),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
 
 
 def build_args(cli, world_size: int):
@@ -71,6 +108,14 @@ def build_args(cli, world_size: int):
 
 def main():
     cli = parse_cli()
+    if cli.dump_outputs is not None:
+        # Random-pixel episodes make the unrolled inner loop chaotic: with the
+        # default fp32-atomic reductions two identical runs differ by more
+        # than the logits' own magnitude after a single step.  A dump run
+        # therefore uses the ordered reductions (bitwise repeatable, ~1.5 %
+        # slower on MI355X) unless the caller has chosen the mode already.
+        os.environ.setdefault("MAML355_DETERMINISTIC", "1")
+    deterministic = os.environ.get("MAML355_DETERMINISTIC", "0") == "1"
     dist_ctx = init_distributed()
     world = dist_ctx.world_size
     args = build_args(cli, world)
@@ -88,7 +133,7 @@ def main():
                for b in stream.get_train_batches(n_distinct)]
 
     def step(i: int):
-        model.run_train_iter(batches[i % n_distinct], epoch=0)
+        return model.run_train_iter(batches[i % n_distinct], epoch=0)
 
     for i in range(cli.warmup):
         step(i)
@@ -96,9 +141,10 @@ def main():
     dist_ctx.barrier()
     if on_gpu:
         torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     for i in range(cli.steps):
-        step(cli.warmup + i)
+        last = step(cli.warmup + i)
     if on_gpu:
         torch.cuda.synchronize()
     dist_ctx.barrier()
@@ -117,6 +163,9 @@ def main():
     value = tasks_per_iter * cli.steps / elapsed
     ms_per_step = elapsed / cli.steps * 1000.0
 
+    if cli.dump_outputs is not None:
+        dump_outputs(cli.dump_outputs, dist_ctx.rank, *last)
+
     if dist_ctx.rank == 0:
         print(json.dumps({
             "metric": "meta-tasks/sec",
@@ -131,6 +180,7 @@ def main():
             "vs_baseline": None,
             "dtype": "bf16" if on_gpu else "fp32",
             "data": "synthetic",
+            "deterministic_reductions": deterministic,
             "config": {
                 "model": cli.model,
                 "global_batch": args.batch_size,

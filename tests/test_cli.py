@@ -7,6 +7,10 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the child runs the CPU path: kernels off, and no device visible to it even
+# where the machine has one
+CPU_ONLY_ENV = {"MAML355_NO_HIP": "1", "HIP_VISIBLE_DEVICES": "-1",
+                "CUDA_VISIBLE_DEVICES": "-1"}
 
 
 def test_train_maml_system_cli(tmp_path):
@@ -30,7 +34,7 @@ def test_train_maml_system_cli(tmp_path):
     }
     cfg_path = tmp_path / "cfg.json"
     cfg_path.write_text(json.dumps(cfg))
-    env = dict(os.environ, MAML355_NO_HIP="1")
+    env = dict(os.environ, **CPU_ONLY_ENV)
     out = subprocess.run(
         [sys.executable, os.path.join(REPO, "train_maml_system.py"),
          "--name_of_args_json_file", str(cfg_path)],

@@ -38,10 +38,10 @@ def test_json_overrides_and_bool_coercion(tmp_path):
 def test_reference_config_files_load():
     """Every shipped reference config must parse through our config system
     (JSON-schema compatibility)."""
-    ref_dir = "/root/reference/experiment_config"
-    if not os.path.isdir(ref_dir):
-        return
-    files = sorted(os.listdir(ref_dir))[:6]
+    ref_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                           "golden", "reference_experiment_config")
+    files = sorted(os.listdir(ref_dir))
+    assert len(files) == 6
     for fname in files:
         args = get_args(["--name_of_args_json_file", os.path.join(ref_dir, fname)])
         assert args.total_epochs == 100
