@@ -81,7 +81,11 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
     if _want_hip(x):
         from . import hip_autograd
         return hip_autograd.task_conv3x3(x, w, b, stride, padding, return_stats)
-    y = ref.task_conv3x3(x, w, b, stride, padding)
+    # kernels disabled with bf16 activations: the fp32 arena views are cast
+    # like the grouped-ATen fallback does (no-op for the fp32 CPU path)
+    y = ref.task_conv3x3(x, w.to(x.dtype),
+                         b.to(x.dtype) if b is not None else None,
+                         stride, padding)
     return (y, None) if return_stats else y
 
 
@@ -117,6 +121,10 @@ def task_maxpool2x2(x):
 
 
 def task_global_avgpool(x):
+    # kernel path is bf16-only; CPU and fp32 inputs stay on the reference
+    if x.dtype == torch.bfloat16 and _want_hip(x):
+        from . import hip_autograd
+        return hip_autograd.task_global_avgpool(x)
     return ref.task_global_avgpool(x)
 
 
@@ -124,7 +132,8 @@ def task_linear(x, w, b=None):
     if _want_hip(x):
         from . import hip_autograd
         return hip_autograd.task_linear(x, w, b)
-    return ref.task_linear(x, w, b)
+    return ref.task_linear(x, w.to(x.dtype),
+                           b.to(x.dtype) if b is not None else None)
 
 
 def softmax_cross_entropy(logits, labels):

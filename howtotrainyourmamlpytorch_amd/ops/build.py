@@ -26,6 +26,8 @@ SOURCES = [
     os.path.join(HIP_DIR, "adam.hip"),
     os.path.join(HIP_DIR, "dconv.hip"),
     os.path.join(HIP_DIR, "linear.hip"),
+    os.path.join(HIP_DIR, "sconv.hip"),
+    os.path.join(HIP_DIR, "gavgpool.hip"),
 ]
 
 

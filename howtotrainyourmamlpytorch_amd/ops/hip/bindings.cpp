@@ -63,6 +63,17 @@ std::vector<torch::Tensor> tconv_mm_v2(torch::Tensor x, torch::Tensor wimg,
                                        long pad, long Ho, long Wo, long Co,
                                        bool with_stats);
 std::vector<torch::Tensor> mfma_probe(torch::Tensor A, torch::Tensor B);
+// sconv.hip
+torch::Tensor sconv_repack(torch::Tensor w, bool dgrad);
+torch::Tensor sconv_fwd(torch::Tensor x, torch::Tensor wp,
+                        c10::optional<torch::Tensor> bias, long pad);
+torch::Tensor sconv_dgrad(torch::Tensor dy, torch::Tensor wp, long pad,
+                          long H, long W);
+std::vector<torch::Tensor> sconv_wgrad(torch::Tensor dy, torch::Tensor x,
+                                       long pad, bool with_bias);
+// gavgpool.hip
+torch::Tensor gavgpool_fwd(torch::Tensor x);
+torch::Tensor gavgpool_bwd(torch::Tensor dy, long H, long W);
 // adam.hip
 void adam_step(std::vector<torch::Tensor> params,
                std::vector<torch::Tensor> grads,
@@ -99,5 +110,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lin_dx", &lin_dx, "linear head input-grad");
   m.def("lin_wgrad", &lin_wgrad, "linear head weight/bias grads");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
-  m.def("adam_step", &adam_step, "fused multi-tensor Adam + grad clamp");
+  m.def("sconv_repack", &sconv_repack,
+        "repack conv weights for the stride-2 MFMA kernels (fwd/dgrad)");
+  m.def("sconv_fwd", &sconv_fwd, "task-batched MFMA stride-2 3x3 conv fwd");
+  m.def("sconv_dgrad", &sconv_dgrad,
+        "stride-2 3x3 conv input-grad (four parity sub-GEMMs)");
+  m.def("sconv_wgrad", &sconv_wgrad, "stride-2 3x3 conv weight/bias grads");
+  m.def("gavgpool_fwd", &gavgpool_fwd, "NHWC global average pool fwd");
+  m.def("gavgpool_bwd", &gavgpool_bwd, "NHWC global average pool bwd");
+  m.def("adam_step",&adam_step, "fused multi-tensor Adam + grad clamp");
 }

@@ -113,8 +113,8 @@ __global__ void wgrad_finalize_kernel(const float* __restrict__ acc,
 //   Wp [T, 9, Ci, Co]      bf16 (repacked; flipped/transposed for dgrad)
 //   bias [T, Co] fp32 or nullptr
 //   Y  [T, NB, Ho, Wo, Co] bf16
-// pad is the im2col pad (fwd: p; dgrad: 2-p).  stride==1 only (stride-2
-// configs use the ATen fallback path).
+// pad is the im2col pad (fwd: p; dgrad: 2-p).  stride==1 only (the
+// stride-2 trio of the max_pooling=False backbone lives in sconv.hip).
 // ---------------------------------------------------------------------------
 #define BM 256
 #define BK 64    // K-step: 2 MFMA K-slices per barrier

@@ -5,18 +5,20 @@ through the inner-loop support forward):
 
 * the conv trio (fwd/dgrad/wgrad) is mutually bilinear — each backward
   composes the other two kernels, so convs run on custom kernels at every
-  derivative order;
+  derivative order; the stride-2 trio of the max_pooling=False backbone
+  (sconv.hip) is composed the same way;
 * BN+act and softmax-CE make their *first backward* its own Function
   whose backward evaluates the analytic closed-form second derivative
   (bn_dbwd.hip / ce_dbwd) — also custom kernels at every order;
 * LSLR update and maxpool are bilinear in their saved tensors — custom at
-  every order;
+  every order; the global average pool is linear (backward = broadcast
+  kernel, whose backward is the forward kernel again);
 * the fused BN+act+pool op uses a single-pass fused backward when the
   backward itself is not being differentiated, and composes the
   individual Functions under create_graph.
 
-Stride-2 convs (max_pooling=False configs) and fp32 compute fall back to
-the grouped-ATen composition.
+Convs with a stride other than 1 or 2, more than 64 channels, or fp32
+compute fall back to the grouped-ATen composition, with a warning.
 """
 
 from __future__ import annotations
@@ -198,6 +200,39 @@ def task_maxpool2x2(x):
     T, NS, H, W, C = x.shape
     y = _PoolFn.apply(x.reshape(T * NS, H, W, C).contiguous())
     return y.view(T, NS, H // 2, W // 2, C)
+
+
+# ---------------------------------------------------------------------------
+# global average pool (max_pooling=False backbone) — linear: the backward
+# is the broadcast kernel, and the backward of that is the forward kernel
+# applied to the incoming grad.
+# ---------------------------------------------------------------------------
+class _GAvgPoolBwdFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dy, H, W):
+        return _ext().gavgpool_bwd(dy, H, W)
+
+    @staticmethod
+    def backward(ctx, ddx):
+        return _GAvgPoolFn.apply(ddx.contiguous()), None, None
+
+
+class _GAvgPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x4):
+        ctx.HW = (x4.shape[1], x4.shape[2])
+        return _ext().gavgpool_fwd(x4)
+
+    @staticmethod
+    def backward(ctx, dy):
+        H, W = ctx.HW
+        return _GAvgPoolBwdFn.apply(dy.contiguous(), H, W)
+
+
+def task_global_avgpool(x):
+    T, NS, H, W, C = x.shape
+    y = _GAvgPoolFn.apply(x.reshape(T * NS, H, W, C).contiguous())
+    return y.view(T, NS, C)
 
 
 # ---------------------------------------------------------------------------
@@ -403,6 +438,87 @@ class _ConvWgradFn(torch.autograd.Function):
         return d_dy, d_x, None, None
 
 
+# ---------------------------------------------------------------------------
+# stride-2 conv trio (max_pooling=False backbone) — sconv.hip.  Composed
+# exactly like the stride-1 trio above: mutually bilinear, each backward
+# calls the other two, custom kernels at every derivative order.  dgrad
+# carries (H, W) explicitly: two input sizes share one Ho under stride 2.
+# ---------------------------------------------------------------------------
+class _SConvFwdFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, pad):
+        ctx.save_for_backward(x, w)
+        ctx.pad = pad
+        ctx.has_bias = b is not None
+        wp = _ext().sconv_repack(w, False)
+        return _ext().sconv_fwd(x, wp, b, pad)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = _SConvDgradFn.apply(dy, w, ctx.pad, x.shape[2], x.shape[3])
+        if ctx.needs_input_grad[1]:
+            want_bias = ctx.has_bias and ctx.needs_input_grad[2]
+            dw, db = _SConvWgradFn.apply(dy, x, ctx.pad, want_bias)
+            if not want_bias:
+                db = None
+        elif ctx.has_bias and ctx.needs_input_grad[2]:
+            db = dy.float().sum(dim=(1, 2, 3))
+        return dx, dw, db, None
+
+
+class _SConvDgradFn(torch.autograd.Function):
+    """dx = dgrad_s2(dy, w): four parity sub-GEMMs in one launch."""
+
+    @staticmethod
+    def forward(ctx, dy, w, pad, H, W):
+        ctx.save_for_backward(dy, w)
+        ctx.pad = pad
+        wp = _ext().sconv_repack(w, True)
+        return _ext().sconv_dgrad(dy, wp, pad, H, W)
+
+    @staticmethod
+    def backward(ctx, g):
+        dy, w = ctx.saved_tensors
+        g = g.contiguous()
+        d_dy = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_dy = _SConvFwdFn.apply(g, w, None, ctx.pad)
+        if ctx.needs_input_grad[1]:
+            d_w = _SConvWgradFn.apply(dy, g, ctx.pad, False)[0]
+        return d_dy, d_w, None, None, None
+
+
+class _SConvWgradFn(torch.autograd.Function):
+    """(dy, x) -> (dw, db) with the bias gradient fused, as _ConvWgradFn."""
+
+    @staticmethod
+    def forward(ctx, dy, x, pad, with_bias):
+        ctx.save_for_backward(dy, x)
+        ctx.pad = pad
+        dw, db = _ext().sconv_wgrad(dy, x, pad, with_bias)
+        return dw, db
+
+    @staticmethod
+    def backward(ctx, gw, gdb):
+        dy, x = ctx.saved_tensors
+        d_dy = d_x = None
+        if ctx.needs_input_grad[0]:
+            if gw is not None:
+                d_dy = _SConvFwdFn.apply(x, gw.contiguous(), None, ctx.pad)
+            if gdb is not None:
+                T, F = gdb.shape
+                add = gdb.view(T, 1, 1, 1, F).to(dy.dtype)
+                d_dy = add.expand_as(dy).contiguous() if d_dy is None else d_dy + add
+        if ctx.needs_input_grad[1] and gw is not None:
+            d_x = _SConvDgradFn.apply(dy, gw.contiguous(), ctx.pad,
+                                      x.shape[2], x.shape[3])
+        return d_dy, d_x, None, None
+
+
 _FALLBACK_WARNED = set()
 
 
@@ -418,11 +534,13 @@ def _warn_fallback(reason: str) -> None:
 
 def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
     # w is task-batched [T, F, C, 3, 3]: dim 1 = out-channels, dim 2 = in
-    if stride != 1 or x.dtype != torch.bfloat16 or w.shape[1] > 64 or w.shape[2] > 64:
-        # stride-2 (max_pooling=False configs), fp32 compute and >64-channel
-        # shapes use the grouped-ATen composition; loud, not silent
-        if stride != 1:
-            _warn_fallback("stride != 1")
+    strided_ok = stride == 2 and padding in (0, 1)
+    if (not (stride == 1 or strided_ok) or x.dtype != torch.bfloat16
+            or w.shape[1] > 64 or w.shape[2] > 64):
+        # strides other than 1/2, fp32 compute and >64-channel shapes use
+        # the grouped-ATen composition; loud, not silent
+        if not (stride == 1 or strided_ok):
+            _warn_fallback(f"stride {stride}, padding {padding}")
         elif x.dtype != torch.bfloat16:
             _warn_fallback(f"dtype {x.dtype}")
         else:
@@ -432,6 +550,17 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
         y = ref.task_conv3x3(x, wc, bc, stride, padding)
         return (y, None) if return_stats else y
     C, F = w.shape[2], w.shape[1]
+    if stride == 2:
+        # max_pooling=False backbone: the stride-2 MFMA trio.  First-layer
+        # C in {1,3} is zero-padded to 8 channels (vector staging), as for
+        # stride 1.  No BN-stats epilogue here: return_stats yields no sums.
+        if C < 8:
+            x = torch.nn.functional.pad(x, (0, 8 - C))
+            w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 8 - C))
+        y = _SConvFwdFn.apply(x.contiguous(), w.contiguous(),
+                              b.contiguous() if b is not None else None,
+                              padding)
+        return (y, None) if return_stats else y
     if C < 8 and not _dconv_ok(C, F):
         # small C without a direct-kernel instantiation: zero-pad to 8 so
         # the vectorized 8-channel GEMM staging applies.  F.pad is

@@ -1,6 +1,8 @@
 """Isolated kernel micro-benchmarks on flagship shapes (run on MI355X):
 
     python tools/bench_kernels.py
+    python tools/bench_kernels.py --strided         # max_pooling=False stages
+    python tools/bench_kernels.py --strided-model   # ... plus whole-model A/B
 
 Prints per-kernel time, effective TFLOP/s (conv) or TB/s (memory-bound),
 so optimization effort goes where the roofline says.
@@ -91,9 +93,180 @@ def bench_pool(N, H, W, C, tag):
           f"{1.875*nbytes/t_b/1e12:5.2f}TB/s")
 
 
+def _median_rounds(fns, rounds=5, reps=20, warmup=5):
+    """Interleaved A/B timing: every round times each variant once, so
+    clock and neighbour noise hit all of them alike; returns the median
+    per-call time of each variant."""
+    for fn in fns:
+        timeit(fn, reps=warmup, warmup=0)
+    ts = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            ts[i].append(timeit(fn, reps=reps, warmup=1))
+    return [sorted(t)[len(t) // 2] for t in ts]
+
+
+def bench_sconv(T, NB, H, W, C, F, tag, pad=1):
+    """Stride-2 conv trio (sconv.hip, through the same entry points the
+    autograd Functions use, repack and first-layer channel pad included)
+    against the grouped-ATen composition ``ref.task_conv3x3(stride=2)`` in
+    bf16 at the same shape — fwd, dgrad and wgrad timed separately."""
+    from howtotrainyourmamlpytorch_amd.ops import reference as ref
+    dev = torch.device("cuda")
+    ext = hip_ext()
+    x = torch.randn(T, NB, H, W, C, device=dev).to(torch.bfloat16)
+    w = torch.randn(T, F, C, 3, 3, device=dev).mul(0.1)
+    b = torch.randn(T, F, device=dev)
+    Ho, Wo = (H + 2 * pad - 3) // 2 + 1, (W + 2 * pad - 3) // 2 + 1
+    dy = torch.randn(T, NB, Ho, Wo, F, device=dev).to(torch.bfloat16)
+    flops = 2.0 * T * NB * Ho * Wo * F * 9 * C
+    first = C < 8   # first layer: no dgrad in the net (x is the image)
+
+    def k_fwd():
+        with torch.no_grad():
+            ops.task_conv3x3(x, w, b, stride=2, padding=pad)
+
+    xk = torch.nn.functional.pad(x, (0, 8 - C)) if first else x
+    wk = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 8 - C)) if first else w
+
+    def k_dgrad():
+        ext.sconv_dgrad(dy, ext.sconv_repack(wk, True), pad, H, W)
+
+    def k_wgrad():
+        ext.sconv_wgrad(dy, xk, pad, True)
+
+    xr = x.clone().requires_grad_(True)
+    wr = w.to(torch.bfloat16).requires_grad_(True)
+    br = b.to(torch.bfloat16).requires_grad_(True)
+    yr = ref.task_conv3x3(xr, wr, br, 2, pad)
+
+    def r_fwd():
+        with torch.no_grad():
+            ref.task_conv3x3(x, w.to(torch.bfloat16), b.to(torch.bfloat16), 2, pad)
+
+    def r_dgrad():
+        torch.autograd.grad(yr, xr, dy, retain_graph=True)
+
+    def r_wgrad():
+        torch.autograd.grad(yr, (wr, br), dy, retain_graph=True)
+
+    kf, rf = _median_rounds([k_fwd, r_fwd])
+    kw, rw = _median_rounds([k_wgrad, r_wgrad])
+    line = (f"[sconv {tag}] T{T} NB{NB} {H}x{W} C{C}->F{F} | "
+            f"fwd kernel {kf*1e6:7.1f}us {flops/kf/1e12:5.1f}TF "
+            f"fallback {rf*1e6:8.1f}us x{rf/kf:5.1f} | ")
+    if first:
+        line += "dgrad n/a (image input) | "
+    else:
+        kd, rd = _median_rounds([k_dgrad, r_dgrad])
+        line += (f"dgrad kernel {kd*1e6:7.1f}us {flops/kd/1e12:5.1f}TF "
+                 f"fallback {rd*1e6:8.1f}us x{rd/kd:5.1f} | ")
+    line += (f"wgrad kernel {kw*1e6:7.1f}us {flops/kw/1e12:5.1f}TF "
+             f"fallback {rw*1e6:8.1f}us x{rw/kw:5.1f}")
+    print(line, flush=True)
+
+
+def bench_gavgpool(N, H, W, C, tag):
+    dev = torch.device("cuda")
+    ext = hip_ext()
+    x = torch.randn(N, H, W, C, device=dev).to(torch.bfloat16)
+    dy = torch.randn(N, C, device=dev).to(torch.bfloat16)
+    kf, rf = _median_rounds([lambda: ext.gavgpool_fwd(x),
+                             lambda: x.mean(dim=(1, 2))])
+    kb, rb = _median_rounds([
+        lambda: ext.gavgpool_bwd(dy, H, W),
+        lambda: (dy.view(N, 1, 1, C) / (H * W)).expand(N, H, W, C).contiguous()])
+    print(f"[gavgpool {tag}] N{N} {H}x{W} C{C} | fwd kernel {kf*1e6:6.1f}us "
+          f"x.mean {rf*1e6:6.1f}us | bwd kernel {kb*1e6:6.1f}us "
+          f"torch {rb*1e6:6.1f}us", flush=True)
+
+
+def bench_strided_model(model_name, tasks_per_gpu, steps=3, warmup=2, rounds=3):
+    """Whole-model second-order MSL step of the max_pooling=False backbone
+    on synthetic episodes (bench.py's configuration with that one flag
+    flipped): the kernel routing against the routing it replaces (grouped-
+    ATen stride-2 conv + x.mean pool), interleaved in one process."""
+    import argparse
+    import bench
+    from howtotrainyourmamlpytorch_amd.data import SyntheticEpisodeStream
+    from howtotrainyourmamlpytorch_amd.meta.engine import MAMLFewShotClassifier
+    from howtotrainyourmamlpytorch_amd.ops import hip_autograd
+    from howtotrainyourmamlpytorch_amd.ops import reference as ref
+
+    cli = argparse.Namespace(model=model_name, tasks_per_gpu=tasks_per_gpu,
+                             inner_steps=5, second_order="True")
+    args = bench.build_args(cli, 1)
+    args.max_pooling = False
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = MAMLFewShotClassifier(
+        im_shape=(2, args.image_channels, args.image_height, args.image_width),
+        device=dev, args=args)
+    stream = SyntheticEpisodeStream(args)
+    batches = [tuple(t.to(dev) for t in b) for b in stream.get_train_batches(4)]
+
+    kernel_conv, kernel_pool = hip_autograd.task_conv3x3, ops.task_global_avgpool
+
+    def old_conv(x, w, b=None, stride=1, padding=1, return_stats=False):
+        if stride == 1:
+            return kernel_conv(x, w, b, stride, padding, return_stats)
+        y = ref.task_conv3x3(x, w.to(x.dtype),
+                             b.to(x.dtype) if b is not None else None,
+                             stride, padding)
+        return (y, None) if return_stats else y
+
+    def run(old):
+        hip_autograd.task_conv3x3 = old_conv if old else kernel_conv
+        ops.task_global_avgpool = ref.task_global_avgpool if old else kernel_pool
+        try:
+            for i in range(warmup):
+                model.run_train_iter(batches[i % 4], epoch=0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(steps):
+                model.run_train_iter(batches[i % 4], epoch=0)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps
+        finally:
+            hip_autograd.task_conv3x3 = kernel_conv
+            ops.task_global_avgpool = kernel_pool
+
+    tk, to = [], []
+    for _ in range(rounds):
+        tk.append(run(False))
+        to.append(run(True))
+    mk, mo = sorted(tk)[len(tk) // 2], sorted(to)[len(to) // 2]
+    print(f"[strided model {model_name}] {tasks_per_gpu} tasks/step, 2nd order "
+          f"MSL | kernels {mk*1e3:8.1f} ms/step {tasks_per_gpu/mk:7.1f} tasks/s | "
+          f"grouped-ATen routing {mo*1e3:8.1f} ms/step "
+          f"{tasks_per_gpu/mo:7.1f} tasks/s | x{mo/mk:.2f}", flush=True)
+
+
+def main_strided(with_model):
+    # mini-imagenet strided stages 84->42->21->11->6, target pass
+    bench_sconv(8, 75, 84, 84, 3, 48, "mi-s0-tgt")
+    bench_sconv(8, 75, 42, 42, 48, 48, "mi-s1-tgt")
+    bench_sconv(8, 75, 21, 21, 48, 48, "mi-s2-tgt")
+    bench_sconv(8, 75, 11, 11, 48, 48, "mi-s3-tgt")
+    # omniglot 20w5s strided stages 28->14->7->4->2, 100-image support
+    bench_sconv(8, 100, 28, 28, 1, 64, "om-s0-sup")
+    bench_sconv(8, 100, 14, 14, 64, 64, "om-s1-sup")
+    bench_sconv(8, 100, 7, 7, 64, 64, "om-s2-sup")
+    bench_sconv(8, 100, 4, 4, 64, 64, "om-s3-sup")
+    bench_gavgpool(8 * 75, 6, 6, 48, "mi-tgt")
+    bench_gavgpool(8 * 100, 2, 2, 64, "om-sup")
+    if with_model:
+        bench_strided_model("maml++_miniimagenet_5w1s", 128)
+        bench_strided_model("maml++_omniglot_20w5s", 128)
+
+
 def main():
     assert torch.cuda.is_available()
     print(torch.cuda.get_device_name(0))
+    if "--strided" in sys.argv or "--strided-model" in sys.argv:
+        # max_pooling=False backbone only: kernels vs the routing they replace
+        main_strided("--strided-model" in sys.argv)
+        return
     # mini-imagenet flagship: 8 tasks/GPU, target pass (75 imgs/task)
     bench_conv(8, 75, 84, 84, 3, 48, "mi-conv0-tgt")
     bench_conv(8, 75, 42, 42, 48, 48, "mi-conv1-tgt")
