@@ -971,15 +971,22 @@ void tconv_wgrad_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ X,
     __syncthreads();
     // stage dY^T, vectorized: slot s -> (kk = s>>3, f0 = (s&7)*8); one
     // bf16x8 load of 8 consecutive f, 8 scalar LDS writes (transpose).
-    // F is always a multiple of 16 here (conv out-channels 48/64), and
-    // rows beyond F are never read by the fragments (mtiles*16 == F).
+    // Rows in [F, mtiles*16) only feed accumulator rows that are never
+    // written out.  F % 8 != 0 (any --cnn_num_filters) loads the last
+    // group element-wise: the vector load would run past the row, and at
+    // the last k past the end of dY.
     for (int s = threadIdx.x; s < WBK * 8; s += blockDim.x) {
       const int kk = s >> 3;
       const int f0 = (s & 7) * 8;
       if (f0 >= F) continue;
       bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
       if (ktab_n[kk] >= 0) {
-        v = *(const bf16x8*)&((const short*)dYt)[(k0 + kk) * F + f0];
+        const short* src = &((const short*)dYt)[(k0 + kk) * F + f0];
+        if (f0 + 8 <= F) {
+          v = *(const bf16x8*)src;
+        } else {
+          for (int j = 0; j < 8 && f0 + j < F; ++j) v[j] = src[j];
+        }
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j)

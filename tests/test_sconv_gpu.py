@@ -102,6 +102,36 @@ def test_sconv_second_order_matches_reference(shape):
         _close(a, r, 8e-2, 5e-2, floor=1e-3)
 
 
+@pytest.mark.parametrize("shape", [(2, 2, 8, 8, 48, 48, 1),
+                                   (2, 2, 9, 7, 16, 32, 0)],
+                         ids=lambda s: "x".join(map(str, s)))
+def test_sconv_second_order_with_updated_bias(shape):
+    """As the inner loop does it: the inner step updates w AND b, so the
+    outer backward reaches _SConvWgradFn.backward with a grad for the
+    fused bias gradient (the ``gdb is not None`` branch)."""
+    T, NB, H, W, C, F, pad = shape
+    x, w, b = _mk(T, NB, H, W, C, F, pad, seed=4)
+    w.requires_grad_(True); b.requires_grad_(True)
+
+    def inner_outer(opmod, x_, w_, b_):
+        y = opmod.task_conv3x3(x_, w_, b_, stride=2, padding=pad)
+        loss = (y.float() ** 2).mean()
+        gw, gb = torch.autograd.grad(loss, (w_, b_), create_graph=True)
+        w2, b2 = w_ - 0.1 * gw, b_ - 0.1 * gb
+        y2 = opmod.task_conv3x3(x_, w2.to(w_.dtype), b2.to(b_.dtype),
+                                stride=2, padding=pad)
+        outer = (y2.float() ** 2).mean()
+        return torch.autograd.grad(outer, (w_, b_))
+
+    gw, gb = inner_outer(ops, x, w, b)
+    xr = x.detach().float().cpu()
+    wr = w.detach().cpu().requires_grad_(True)
+    br = b.detach().cpu().requires_grad_(True)
+    gwr, gbr = inner_outer(ref, xr, wr, br)
+    for a, r in ((gw.cpu(), gwr), (gb.cpu(), gbr)):
+        _close(a, r, 8e-2, 5e-2, floor=1e-3)
+
+
 def test_sconv_second_order_through_input():
     """create_graph through dgrad: the grad of ||dx||^2 w.r.t. w and the
     upstream grad exercises _SConvDgradFn.backward (fwd + wgrad kernels)."""
