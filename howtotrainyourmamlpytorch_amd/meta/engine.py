@@ -326,6 +326,8 @@ class MAMLFewShotClassifier(nn.Module):
     # (``few_shot_learning_system.py:399-424``):
     #   classifier.layer_dict.conv{i}.conv.{weight,bias}
     #   classifier.layer_dict.conv{i}.norm_layer.{weight,bias,running_*}
+    #     (layer norm: weight = ones and bias, both (F, Ho, Wo) — the
+    #     reference's CHW feature shape; ours is HWC)
     #   classifier.layer_dict.linear.{weights,bias}
     #   inner_loop_optimizer.names_learning_rates_dict.layer_dict-...-weight
     # The flat arena is expanded on save and re-packed on load; the linear
@@ -357,6 +359,8 @@ class MAMLFewShotClassifier(nn.Module):
             t = v.clone()
             if name == "layer_dict.linear.weights":
                 t = self._linear_to_reference(t)
+            elif cls.norm_layer_type == "layer_norm" and name.endswith("norm_layer.bias"):
+                t = t.permute(2, 0, 1).contiguous()      # HWC -> CHW
             out["classifier." + name] = t
         if cls.norm_layer_type == "batch_norm":
             for i in range(cls.num_stages):
@@ -366,6 +370,13 @@ class MAMLFewShotClassifier(nn.Module):
                     out[prefix + "bias"] = getattr(cls, f"bn_bias_{i}").detach().clone()
                 out[prefix + "running_mean"] = getattr(cls, f"bn_running_mean_{i}").clone()
                 out[prefix + "running_var"] = getattr(cls, f"bn_running_var_{i}").clone()
+        if cls.norm_layer_type == "layer_norm":
+            for i in range(cls.num_stages):
+                prefix = f"classifier.layer_dict.conv{i}.norm_layer."
+                if not cls.inner_loop_bn_params:
+                    out[prefix + "bias"] = (cls.ln_bias(i).detach()
+                                            .permute(2, 0, 1).contiguous().clone())
+                out[prefix + "weight"] = torch.ones_like(out[prefix + "bias"])
         for spec in cls.arena.specs:
             key = ("inner_loop_optimizer.names_learning_rates_dict."
                    + spec.name.replace(".", "-"))
@@ -375,7 +386,17 @@ class MAMLFewShotClassifier(nn.Module):
     def load_reference_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         cls = self.classifier
         named = {}
+        layer_norm = cls.norm_layer_type == "layer_norm"
         for spec in cls.arena.specs:
+            if layer_norm and spec.name.endswith("norm_layer.bias"):
+                # CHW -> our HWC; a checkpoint from before the bias existed
+                # has no such key and leaves the bias as it is (zero)
+                if "classifier." + spec.name in sd:
+                    t = sd["classifier." + spec.name].permute(1, 2, 0)
+                else:
+                    t = cls.arena.views(cls.theta.detach())[spec.name]
+                named[spec.name] = t
+                continue
             t = sd["classifier." + spec.name]
             if spec.name == "layer_dict.linear.weights":
                 t = self._linear_from_reference(t)
@@ -391,6 +412,12 @@ class MAMLFewShotClassifier(nn.Module):
                     if prefix + "running_mean" in sd:
                         getattr(cls, f"bn_running_mean_{i}").copy_(sd[prefix + "running_mean"])
                         getattr(cls, f"bn_running_var_{i}").copy_(sd[prefix + "running_var"])
+            if layer_norm and not cls.inner_loop_bn_params:
+                # the frozen all-ones weight is not stored anywhere
+                for i in range(cls.num_stages):
+                    key = f"classifier.layer_dict.conv{i}.norm_layer.bias"
+                    if key in sd:
+                        cls.ln_bias(i).copy_(sd[key].permute(1, 2, 0))
             for spec in cls.arena.specs:
                 key = ("inner_loop_optimizer.names_learning_rates_dict."
                        + spec.name.replace(".", "-"))

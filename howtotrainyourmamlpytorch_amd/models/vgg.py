@@ -60,8 +60,10 @@ class TaskBatchedVGG(nn.Module):
 
     Inner-loop-adapted params (the arena): conv weights/biases + linear
     weight/bias (+ norm-layer affine params when
-    ``enable_inner_loop_optimizable_bn_params``).  Meta-only params: the
-    arena init ``theta`` plus per-step BN gamma/beta.
+    ``enable_inner_loop_optimizable_bn_params``: BN gamma/beta, or the
+    layer norm's elementwise bias).  Meta-only params: the arena init
+    ``theta`` plus per-step BN gamma/beta, or the layer-norm biases
+    ``ln_bias_{i}`` when they are not inner-loop fast weights.
     """
 
     def __init__(self, im_shape: Tuple[int, int, int], num_output_classes: int,
@@ -94,11 +96,14 @@ class TaskBatchedVGG(nn.Module):
         stride = 1 if max_pooling else 2
         h, w = self.im_h, self.im_w
         self.stage_shapes: List[Tuple[int, int, int]] = []  # (C_in, H_in, W_in) per stage
+        # post-conv (pre-pool) spatial size per stage: what the norm layer sees
+        self.conv_out_shapes: List[Tuple[int, int]] = []
         c = self.im_c
         for i in range(num_stages):
             self.stage_shapes.append((c, h, w))
             h = (h + 2 * pad - 3) // stride + 1
             w = (w + 2 * pad - 3) // stride + 1
+            self.conv_out_shapes.append((h, w))
             if max_pooling:
                 h, w = h // 2, w // 2
             if h < 1 or w < 1:
@@ -122,6 +127,15 @@ class TaskBatchedVGG(nn.Module):
                 bn_shape = (num_filters,)
                 named_shapes.append((f"layer_dict.conv{i}.norm_layer.weight", bn_shape))
                 named_shapes.append((f"layer_dict.conv{i}.norm_layer.bias", bn_shape))
+            elif inner_loop_bn_params and norm_layer == "layer_norm":
+                # the reference's layer norm has a frozen weight and an
+                # elementwise bias of the post-conv feature shape (C, h, w)
+                # (meta_neural_network_architectures.py:261-322); only the
+                # bias has requires_grad, so only it becomes a fast weight.
+                # Stored in our HWC order.
+                ho, wo = self.conv_out_shapes[i]
+                named_shapes.append((f"layer_dict.conv{i}.norm_layer.bias",
+                                     (ho, wo, num_filters)))
         # linear head: weight stored [ways, K] with K = NHWC-flattened feature
         named_shapes.append(("layer_dict.linear.weights", (num_output_classes, self.feature_dim)))
         named_shapes.append(("layer_dict.linear.bias", (num_output_classes,)))
@@ -137,6 +151,10 @@ class TaskBatchedVGG(nn.Module):
                 bn_shape = (num_filters,)
                 init[f"layer_dict.conv{i}.norm_layer.weight"] = torch.ones(*bn_shape)
                 init[f"layer_dict.conv{i}.norm_layer.bias"] = torch.zeros(*bn_shape)
+            elif inner_loop_bn_params and norm_layer == "layer_norm":
+                ho, wo = self.conv_out_shapes[i]
+                init[f"layer_dict.conv{i}.norm_layer.bias"] = torch.zeros(
+                    ho, wo, num_filters)
         init["layer_dict.linear.weights"] = _xavier_uniform(
             (num_output_classes, self.feature_dim), generator)
         init["layer_dict.linear.bias"] = torch.zeros(num_output_classes)
@@ -154,6 +172,12 @@ class TaskBatchedVGG(nn.Module):
                                         nn.Parameter(g, requires_grad=learnable_bn_gamma))
                 self.register_parameter(f"bn_bias_{i}",
                                         nn.Parameter(b, requires_grad=learnable_bn_beta))
+        if norm_layer == "layer_norm" and not inner_loop_bn_params:
+            # meta-only elementwise bias [Ho, Wo, F], learned by the outer loop
+            for i in range(num_stages):
+                ho, wo = self.conv_out_shapes[i]
+                self.register_parameter(
+                    f"ln_bias_{i}", nn.Parameter(torch.zeros(ho, wo, num_filters)))
         if norm_layer == "batch_norm":
             steps_dim = (num_steps,) if per_step_bn_statistics else ()
             for i in range(num_stages):
@@ -228,11 +252,9 @@ class TaskBatchedVGG(nn.Module):
                 self._update_running_stats(i, num_step, mean, var,
                                            count=stat_count)
             elif self.norm_layer_type == "layer_norm":
-                wname = f"layer_dict.conv{i}.norm_layer.bias"
-                bias = v[wname] if wname in v else torch.zeros(
-                    out.shape[-1], device=out.device, dtype=torch.float32)
-                weight = torch.ones_like(bias)
-                out = ops.task_layer_norm_act(out, weight, bias,
+                # weight frozen at 1 (None); bias [T, Ho, Wo, F] arena view
+                # or the shared meta-only [Ho, Wo, F] parameter
+                out = ops.task_layer_norm_act(out, None, self.ln_bias(i, v),
                                               eps=self.bn_eps, negative_slope=self.negative_slope)
             else:
                 out = torch.nn.functional.leaky_relu(out, negative_slope=self.negative_slope)
@@ -264,6 +286,17 @@ class TaskBatchedVGG(nn.Module):
             gamma = gamma[num_step]          # [F]
             beta = beta[num_step]
         return gamma, beta
+
+    def ln_bias(self, i: int, v: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+        """The layer-norm bias of stage i in HWC order: the arena view
+        (``[T, Ho, Wo, F]`` for a ``[T, P]`` arena; theta's own view when
+        ``v`` is None) when it is an inner-loop fast weight, else the
+        meta-only parameter ``ln_bias_{i}``."""
+        if self.inner_loop_bn_params:
+            if v is None:
+                v = self.arena.views(self.theta)
+            return v[f"layer_dict.conv{i}.norm_layer.bias"]
+        return getattr(self, f"ln_bias_{i}")
 
     def _update_running_stats(self, i: int, num_step: int, mean: torch.Tensor,
                               var: torch.Tensor, count: int) -> None:

@@ -97,7 +97,15 @@ def task_bn_act(x, gamma, beta, eps=1e-5, negative_slope=0.01, apply_act=True):
 
 
 def task_layer_norm_act(x, weight, bias, eps=1e-5, negative_slope=0.01, apply_act=True):
-    _want_hip(x)  # layer-norm path: reference composition is acceptable on GPU too
+    """Per-image LayerNorm + bias + leaky-ReLU.  ``weight`` None means 1.
+    The backbone's form — weight None, elementwise bias ``[H, W, C]`` or
+    ``[T, H, W, C]``, bf16 or fp32 — runs on the HIP kernels; every other
+    combination (a weight, a per-channel bias) is the torch composition."""
+    if (weight is None and bias.dim() in (3, 4)
+            and x.dtype in (torch.bfloat16, torch.float32) and _want_hip(x)):
+        from . import hip_autograd
+        return hip_autograd.task_layer_norm_act(x, bias, eps, negative_slope, apply_act)
+    _want_hip(x)  # still refuse a GPU tensor without a loaded extension
     return ref.task_layer_norm_act(x, weight, bias, eps, negative_slope, apply_act)
 
 

@@ -28,6 +28,7 @@ SOURCES = [
     os.path.join(HIP_DIR, "linear.hip"),
     os.path.join(HIP_DIR, "sconv.hip"),
     os.path.join(HIP_DIR, "gavgpool.hip"),
+    os.path.join(HIP_DIR, "layernorm.hip"),
 ]
 
 

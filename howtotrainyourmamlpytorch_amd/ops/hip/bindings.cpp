@@ -32,6 +32,16 @@ std::vector<torch::Tensor> bn_act_dbwd(torch::Tensor x, torch::Tensor u,
                                        torch::Tensor rstd, torch::Tensor gamma,
                                        torch::Tensor beta, torch::Tensor ggam,
                                        torch::Tensor gbet, double slope, bool act);
+// layernorm.hip
+std::vector<torch::Tensor> ln_act_fwd(torch::Tensor x, torch::Tensor bias,
+                                      double eps, double slope, bool act);
+std::vector<torch::Tensor> ln_act_bwd(torch::Tensor dy, torch::Tensor x,
+                                      torch::Tensor mean, torch::Tensor rstd,
+                                      torch::Tensor bias, double slope, bool act);
+std::vector<torch::Tensor> ln_act_dbwd(torch::Tensor x, torch::Tensor dy,
+                                       torch::Tensor gx, torch::Tensor gb,
+                                       torch::Tensor mean, torch::Tensor rstd,
+                                       torch::Tensor bias, double slope, bool act);
 // lslr.hip
 torch::Tensor lslr_fwd(torch::Tensor arena, torch::Tensor grad, torch::Tensor lr_vec);
 std::vector<torch::Tensor> lslr_bwd(torch::Tensor gout, torch::Tensor grad,
@@ -93,6 +103,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_dbwd", &ce_dbwd, "softmax-CE double-backward");
   m.def("bn_act_dbwd", &bn_act_dbwd, "BN+leakyReLU analytic double-backward");
   m.def("ce_bwd", &ce_bwd, "fused softmax-CE bwd");
+  m.def("ln_act_fwd", &ln_act_fwd, "fused task-batched LayerNorm+bias+leakyReLU fwd");
+  m.def("ln_act_bwd", &ln_act_bwd, "fused task-batched LayerNorm+bias+leakyReLU bwd");
+  m.def("ln_act_dbwd", &ln_act_dbwd, "LayerNorm+bias+leakyReLU analytic double-backward");
   m.def("lslr_fwd", &lslr_fwd, "fused LSLR arena update fwd");
   m.def("lslr_bwd", &lslr_bwd, "fused LSLR arena update bwd");
   m.def("tconv_repack", &tconv_repack, "repack conv weights for MFMA (fwd/dgrad)");

@@ -10,6 +10,9 @@ through the inner-loop support forward):
 * BN+act and softmax-CE make their *first backward* its own Function
   whose backward evaluates the analytic closed-form second derivative
   (bn_dbwd.hip / ce_dbwd) — also custom kernels at every order;
+* LayerNorm+bias+act (layernorm.hip) follows the BN pattern: its first
+  backward is its own Function, whose backward is the closed-form
+  ``ln_act_dbwd`` kernel — custom kernels at every order, bf16 and fp32;
 * LSLR update and maxpool are bilinear in their saved tensors — custom at
   every order; the global average pool is linear (backward = broadcast
   kernel, whose backward is the forward kernel again);
@@ -150,6 +153,66 @@ def task_bn_act_pool(x, gamma, beta, eps=1e-5, negative_slope=0.01, sums=None):
     y, mean, var = _BNActPoolFn.apply(x.contiguous(), gamma, beta, eps,
                                       negative_slope, sums)
     return y, mean, var
+
+
+# ---------------------------------------------------------------------------
+# fused LayerNorm (per image, weight 1) + elementwise bias + leaky-ReLU
+# ---------------------------------------------------------------------------
+class _LNBwdFn(torch.autograd.Function):
+    """The first backward of LN+act as its own Function: forward = the bwd
+    kernels; backward = the analytic double-backward kernel.  The bias gets
+    no gradient here (the leaky-ReLU side is held constant), as BN's beta
+    gets none in ``_BNBwdFn``."""
+
+    @staticmethod
+    def forward(ctx, x, bias, u, mean, rstd, slope, act):
+        dx, dbias_t = _ext().ln_act_bwd(u, x, mean, rstd, bias, slope, act)
+        ctx.save_for_backward(x, bias, u, mean, rstd)
+        ctx.slope, ctx.act = slope, act
+        return dx, dbias_t
+
+    @staticmethod
+    def backward(ctx, gx, gb_t):
+        x, bias, u, mean, rstd = ctx.saved_tensors
+        d_u, d_x = _ext().ln_act_dbwd(x, u, gx.contiguous(), gb_t, mean, rstd,
+                                      bias, ctx.slope, ctx.act)
+        return d_x, None, d_u, None, None, None, None
+
+
+class _LNActFn(torch.autograd.Function):
+    """x [T, NS, H, W, C], bias fp32 [D] or [T, D] -> y.  Fused kernels at
+    every order."""
+
+    @staticmethod
+    def forward(ctx, x, bias, eps, slope, act):
+        y, mean, rstd = _ext().ln_act_fwd(x, bias, eps, slope, act)
+        ctx.save_for_backward(x, bias, mean, rstd)
+        ctx.slope, ctx.act = slope, act
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, bias, mean, rstd = ctx.saved_tensors
+        dx, dbias_t = _LNBwdFn.apply(x, bias, dy.contiguous(), mean, rstd,
+                                     ctx.slope, ctx.act)
+        # shared bias: fold the per-task sums over T (outer-dim sum, ordered)
+        dbias = dbias_t if bias.dim() == 2 else dbias_t.sum(0)
+        return dx, dbias, None, None, None
+
+
+def task_layer_norm_act(x, bias, eps=1e-5, negative_slope=0.01, apply_act=True):
+    """bias: [H, W, C] (shared) or [T, H, W, C] (per-task fast weight)."""
+    T, NS, H, W, C = x.shape
+    D = H * W * C
+    if bias.dim() == 3:
+        b2 = bias.reshape(D)
+    elif bias.dim() == 4:
+        b2 = bias.reshape(T, D)
+    else:
+        raise ValueError("task_layer_norm_act: bias must be [H, W, C] or "
+                         "[T, H, W, C], got %s" % (tuple(bias.shape),))
+    return _LNActFn.apply(x.contiguous(), b2.float().contiguous(), eps,
+                          negative_slope, apply_act)
 
 
 # ---------------------------------------------------------------------------

@@ -81,24 +81,36 @@ def task_bn_act(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
     return y.to(x.dtype), mean, var
 
 
-def task_layer_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+def task_layer_norm_act(x: torch.Tensor, weight: Optional[torch.Tensor],
+                        bias: torch.Tensor,
                         eps: float = 1e-5, negative_slope: float = 0.01,
                         apply_act: bool = True) -> torch.Tensor:
     """Task-batched LayerNorm over (H, W, C) per image + leaky-ReLU.
 
     Mirrors the reference's alternative norm (weight frozen at 1, bias
     adaptable — ``meta_neural_network_architectures.py:261-322``).
-    x: [T, NS, H, W, C]; weight/bias: [C]-broadcastable or [T, C].
+    x: [T, NS, H, W, C].  weight: None (= 1), [C] or [T, C].  bias: [C] or
+    [T, C] (per channel), or — the reference's own form, one value per
+    feature — [H, W, C] or [T, H, W, C].
     """
     T, NS, H, W, C = x.shape
     xf = x.float()
     mean = xf.mean(dim=(2, 3, 4), keepdim=True)
     var = xf.var(dim=(2, 3, 4), unbiased=False, keepdim=True)
     y = (xf - mean) * torch.rsqrt(var + eps)
-    if weight.dim() == 1:
-        y = y * weight.view(1, 1, 1, 1, C) + bias.view(1, 1, 1, 1, C)
+    if weight is not None:
+        if weight.dim() == 1:
+            y = y * weight.view(1, 1, 1, 1, C)
+        else:
+            y = y * weight.view(T, 1, 1, 1, C)
+    if bias.dim() == 1:
+        y = y + bias.view(1, 1, 1, 1, C)
+    elif bias.dim() == 2:
+        y = y + bias.view(T, 1, 1, 1, C)
+    elif bias.dim() == 3:
+        y = y + bias.reshape(1, 1, H, W, C)
     else:
-        y = y * weight.view(T, 1, 1, 1, C) + bias.view(T, 1, 1, 1, C)
+        y = y + bias.reshape(T, 1, H, W, C)
     if apply_act:
         y = F.leaky_relu(y, negative_slope=negative_slope)
     return y.to(x.dtype)

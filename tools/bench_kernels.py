@@ -3,6 +3,8 @@
     python tools/bench_kernels.py
     python tools/bench_kernels.py --strided         # max_pooling=False stages
     python tools/bench_kernels.py --strided-model   # ... plus whole-model A/B
+    python tools/bench_kernels.py --ln              # layer-norm kernels vs torch
+    python tools/bench_kernels.py --ln-model        # ... plus whole-model A/B
 
 Prints per-kernel time, effective TFLOP/s (conv) or TB/s (memory-bound),
 so optimization effort goes where the roofline says.
@@ -181,6 +183,149 @@ def bench_gavgpool(N, H, W, C, tag):
           f"torch {rb*1e6:6.1f}us", flush=True)
 
 
+def bench_ln(T, NS, H, W, C, tag, rounds=3, reps=5):
+    """Layer-norm + bias + leaky-ReLU (layernorm.hip) fwd, bwd and dbwd in
+    bf16 against the torch composition ``ref.task_layer_norm_act`` and what
+    autograd composes from it — the routing the kernels replace.  Shared
+    [H, W, C] bias (the default, meta-only form)."""
+    from howtotrainyourmamlpytorch_amd.ops import reference as ref
+    dev = torch.device("cuda")
+    ext = hip_ext()
+    D = H * W * C
+    x = torch.randn(T, NS, H, W, C, device=dev).to(torch.bfloat16)
+    bias = torch.randn(H, W, C, device=dev)
+    dy = torch.randn(T, NS, H, W, C, device=dev).to(torch.bfloat16)
+    gx = torch.randn(T, NS, H, W, C, device=dev).to(torch.bfloat16)
+    gb = torch.randn(H, W, C, device=dev)
+    gb_t = gb.reshape(1, D).expand(T, D).contiguous()
+    b1 = bias.reshape(D)
+    _, mean, rstd = ext.ln_act_fwd(x, b1, 1e-5, 0.01, True)
+    nbytes = T * NS * D * 2
+
+    def k_fwd():
+        ext.ln_act_fwd(x, b1, 1e-5, 0.01, True)
+
+    def k_bwd():
+        ext.ln_act_bwd(dy, x, mean, rstd, b1, 0.01, True)
+
+    def k_dbwd():
+        ext.ln_act_dbwd(x, dy, gx, gb_t, mean, rstd, b1, 0.01, True)
+
+    def r_fwd():
+        with torch.no_grad():
+            ref.task_layer_norm_act(x, None, bias, 1e-5, 0.01, True)
+
+    head = f"[ln {tag}] T{T} NS{NS} {H}x{W}x{C} (D={D}, {T * NS} images)"
+    # timed windows of some 50 ms of kernel work, whatever the shape
+    reps = max(reps, min(200, int(0.05 / timeit(k_dbwd, reps=3, warmup=2))))
+    kf, rf = _median_rounds([k_fwd, r_fwd], rounds, reps, 2)
+    # kernel passes over the data — fwd: x twice, y; bwd: x and dy twice, dx,
+    # x and dy again for dbias; dbwd: x, dy, gx twice, d_dy, d_x
+    print(f"{head} | fwd kernel {kf*1e6:9.1f}us {3*nbytes/kf/1e12:5.2f}TB/s "
+          f"composition {rf*1e6:10.1f}us x{rf/kf:5.1f}", flush=True)
+
+    def composition():
+        xr = x.clone().requires_grad_(True)
+        br = bias.clone().requires_grad_(True)
+        ur = dy.clone().requires_grad_(True)
+        yr = ref.task_layer_norm_act(xr, None, br, 1e-5, 0.01, True)
+
+        def r_bwd():
+            torch.autograd.grad(yr, (xr, br), dy, retain_graph=True)
+
+        kb, rb = _median_rounds([k_bwd, r_bwd], rounds, reps, 2)
+        print(f"{head} | bwd kernel {kb*1e6:9.1f}us {7*nbytes/kb/1e12:5.2f}TB/s "
+              f"composition {rb*1e6:10.1f}us x{rb/kb:5.1f}", flush=True)
+        dxr, dbr = torch.autograd.grad(yr, (xr, br), ur, create_graph=True)
+
+        def r_dbwd():
+            torch.autograd.grad((dxr, dbr), (ur, xr), (gx, gb), retain_graph=True)
+
+        kd, rd = _median_rounds([k_dbwd, r_dbwd], rounds, reps, 2)
+        print(f"{head} | dbwd kernel {kd*1e6:9.1f}us {8*nbytes/kd/1e12:5.2f}TB/s "
+              f"composition {rd*1e6:10.1f}us x{rd/kd:5.1f}", flush=True)
+
+    try:
+        composition()
+        return
+    except torch.cuda.OutOfMemoryError:
+        pass
+    torch.cuda.empty_cache()
+    print(f"{head} | the composition's autograd graph does not fit in memory "
+          f"at this size; kernels alone:", flush=True)
+    kb, = _median_rounds([k_bwd], rounds, reps, 2)
+    kd, = _median_rounds([k_dbwd], rounds, reps, 2)
+    print(f"{head} | bwd kernel {kb*1e6:9.1f}us {7*nbytes/kb/1e12:5.2f}TB/s | "
+          f"dbwd kernel {kd*1e6:9.1f}us {8*nbytes/kd/1e12:5.2f}TB/s", flush=True)
+
+
+def bench_ln_model(model_name, tasks_per_gpu, steps=3, warmup=2, rounds=3):
+    """Whole-model second-order MSL step of the layer-norm backbone on
+    synthetic episodes (bench.py's configuration with --norm_layer
+    layer_norm): the kernels against the torch composition they replace,
+    interleaved in one process."""
+    import argparse
+    import bench
+    from howtotrainyourmamlpytorch_amd.data import SyntheticEpisodeStream
+    from howtotrainyourmamlpytorch_amd.meta.engine import MAMLFewShotClassifier
+    from howtotrainyourmamlpytorch_amd.ops import reference as ref
+
+    cli = argparse.Namespace(model=model_name, tasks_per_gpu=tasks_per_gpu,
+                             inner_steps=5, second_order="True")
+    args = bench.build_args(cli, 1)
+    args.norm_layer = "layer_norm"
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = MAMLFewShotClassifier(
+        im_shape=(2, args.image_channels, args.image_height, args.image_width),
+        device=dev, args=args)
+    stream = SyntheticEpisodeStream(args)
+    batches = [tuple(t.to(dev) for t in b) for b in stream.get_train_batches(4)]
+    kernel_ln = ops.task_layer_norm_act
+
+    def run(old):
+        ops.task_layer_norm_act = ref.task_layer_norm_act if old else kernel_ln
+        try:
+            for i in range(warmup):
+                model.run_train_iter(batches[i % 4], epoch=0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(steps):
+                model.run_train_iter(batches[i % 4], epoch=0)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps
+        finally:
+            ops.task_layer_norm_act = kernel_ln
+
+    tk, to = [], []
+    try:
+        for _ in range(rounds):
+            tk.append(run(False))
+            to.append(run(True))
+    except torch.cuda.OutOfMemoryError:
+        print(f"[ln model {model_name}] {tasks_per_gpu} tasks/step: out of "
+              f"memory (kernel runs so far: {tk})", flush=True)
+        return
+    mk, mo = sorted(tk)[len(tk) // 2], sorted(to)[len(to) // 2]
+    print(f"[ln model {model_name}] {tasks_per_gpu} tasks/step, 2nd order "
+          f"MSL | kernels {mk*1e3:8.1f} ms/step {tasks_per_gpu/mk:7.1f} tasks/s | "
+          f"torch composition {mo*1e3:8.1f} ms/step "
+          f"{tasks_per_gpu/mo:7.1f} tasks/s | x{mo/mk:.2f}", flush=True)
+
+
+def main_ln():
+    # stage-0 layer norm of the two bench workloads at bench.py's 128 tasks
+    # per GPU; the support pass of the second is the few-large-images case
+    # that is split over workgroups
+    bench_ln(128, 20, 28, 28, 64, "om-20w5s-s0-tgt")
+    bench_ln(128, 75, 84, 84, 48, "mi-5w1s-s0-tgt")
+    bench_ln(128, 5, 84, 84, 48, "mi-5w1s-s0-sup")
+    bench_ln(8, 5, 84, 84, 48, "mi-5w1s-s0-sup-8tasks")
+    if "--ln-model" in sys.argv:
+        bench_ln_model("maml++_omniglot_20w5s", 16)
+        bench_ln_model("maml++_miniimagenet_5w1s", 16)
+
+
 def bench_strided_model(model_name, tasks_per_gpu, steps=3, warmup=2, rounds=3):
     """Whole-model second-order MSL step of the max_pooling=False backbone
     on synthetic episodes (bench.py's configuration with that one flag
@@ -263,6 +408,9 @@ def main_strided(with_model):
 def main():
     assert torch.cuda.is_available()
     print(torch.cuda.get_device_name(0))
+    if "--ln" in sys.argv or "--ln-model" in sys.argv:
+        main_ln()
+        return
     if "--strided" in sys.argv or "--strided-model" in sys.argv:
         # max_pooling=False backbone only: kernels vs the routing they replace
         main_strided("--strided-model" in sys.argv)
