@@ -22,6 +22,7 @@ SOURCES = [
     os.path.join(HIP_DIR, "softmax_ce.hip"),
     os.path.join(HIP_DIR, "lslr.hip"),
     os.path.join(HIP_DIR, "tconv.hip"),
+    os.path.join(HIP_DIR, "wgrad_nt.hip"),
     os.path.join(HIP_DIR, "bn_dbwd.hip"),
     os.path.join(HIP_DIR, "adam.hip"),
     os.path.join(HIP_DIR, "dconv.hip"),

@@ -56,6 +56,9 @@ std::vector<torch::Tensor> tconv_wgrad(torch::Tensor dy, torch::Tensor x,
 torch::Tensor tconv_repack_v2(torch::Tensor w, bool dgrad);
 std::vector<torch::Tensor> tconv_wgrad_v2(torch::Tensor dy, torch::Tensor x,
                                           long pad, bool with_bias);
+// wgrad_nt.hip
+std::vector<torch::Tensor> tconv_wgrad_v3(torch::Tensor dy, torch::Tensor x,
+                                          long pad, bool with_bias);
 // dconv.hip
 torch::Tensor dconv_fwd(torch::Tensor x, torch::Tensor w,
                         c10::optional<torch::Tensor> bias, long pad,
@@ -117,6 +120,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "async-pipelined MFMA 3x3 conv fwd/dgrad (v2)");
   m.def("tconv_wgrad_v2", &tconv_wgrad_v2,
         "async-pipelined wgrad via k-contiguous operand transposes (v2)");
+  m.def("tconv_wgrad_v3", &tconv_wgrad_v3,
+        "transpose-free wgrad: operands staged as stored, transposing LDS reads (v3)");
   m.def("dconv_fwd", &dconv_fwd, "direct small-C conv fwd (VALU)");
   m.def("dconv_wgrad", &dconv_wgrad, "direct small-C conv wgrad (VALU)");
   m.def("lin_fwd", &lin_fwd, "task-batched linear head fwd");

@@ -1411,6 +1411,14 @@ std::vector<torch::Tensor> tconv_wgrad_v2(torch::Tensor dy, torch::Tensor x,
   return {dw, db};
 }
 
+// wgrad_finalize_kernel for callers in other translation units (wgrad_nt.hip)
+void launch_wgrad_finalize(const float* acc, float* dw, int T, int F, int C,
+                           int nslices, hipStream_t stream) {
+  const long total = (long)T * F * C * 9;
+  hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(ew_grid2(total, 256)),
+                     dim3(256), 0, stream, acc, dw, T, F, C, nslices);
+}
+
 std::vector<torch::Tensor> mfma_probe(torch::Tensor A, torch::Tensor B) {
   TORCH_CHECK(A.is_cuda() && A.sizes() == torch::IntArrayRef({16, 32}));
   TORCH_CHECK(B.sizes() == torch::IntArrayRef({32, 16}));

@@ -458,6 +458,21 @@ class _ConvDgradFn(torch.autograd.Function):
         return d_dy, d_w, None
 
 
+# v3 has no fixed-cost operand copies, so unlike v2 it needs no lower bound
+# on the reduction length: measured at or ahead of v1 down to the smallest
+# workload shapes (profiles/README.md, "wgrad v3").
+_WGRAD_V3_MIN_POSITIONS = 0
+
+
+def _wgrad_v3_ok(c: int, f: int, positions: int) -> bool:
+    """Transpose-free wgrad (wgrad_nt.hip): 8-aligned F <= 64, 8-aligned C
+    or the first layer's C in {1, 3}.  MAML355_WGRAD_V3=0 restores the
+    v2 / v1 routing below."""
+    return (f % 8 == 0 and f <= 64 and (c % 8 == 0 or c in (1, 3))
+            and positions >= _WGRAD_V3_MIN_POSITIONS
+            and os.environ.get("MAML355_WGRAD_V3", "1") != "0")
+
+
 class _ConvWgradFn(torch.autograd.Function):
     """(dy, x) -> (dw, db); db is the fused bias gradient (sum of dy over
     positions) — the wgrad kernel already stages the dY tiles, so the
@@ -474,6 +489,11 @@ class _ConvWgradFn(torch.autograd.Function):
         if (x.shape[4] <= 8 and dy.shape[4] <= 64
                 and os.environ.get("MAML355_DCONV_WGRAD", "0") == "1"):
             dw, db = _ext().dconv_wgrad(dy, x, pad, with_bias)
+        elif _wgrad_v3_ok(x.shape[4], dy.shape[4],
+                          dy.shape[1] * dy.shape[2] * dy.shape[3]):
+            # v3: both operands staged as stored, the transpose moved into
+            # the LDS read — none of v2's operand copies
+            dw, db = _ext().tconv_wgrad_v3(dy, x, pad, with_bias)
         elif (dy.shape[4] <= 64
                 and dy.shape[1] * dy.shape[2] * dy.shape[3] >= 30000
                 and os.environ.get("MAML355_WGRAD_V2", "1") != "0"):

@@ -5,6 +5,7 @@
     python tools/bench_kernels.py --strided-model   # ... plus whole-model A/B
     python tools/bench_kernels.py --ln              # layer-norm kernels vs torch
     python tools/bench_kernels.py --ln-model        # ... plus whole-model A/B
+    python tools/bench_kernels.py --wgrad           # wgrad v1 / v2 / v3 per shape
 
 Prints per-kernel time, effective TFLOP/s (conv) or TB/s (memory-bound),
 so optimization effort goes where the roofline says.
@@ -60,8 +61,73 @@ def bench_conv(T, NB, H, W, C, F, tag):
               f"dgrad {t_d2*1e6:7.1f}us {flops/t_d2/1e12:6.1f}TF")
     if F <= 64:
         t_w2 = timeit(lambda: ext.tconv_wgrad_v2(dy, x, 1, True))
-        print(f"[conv {tag}]   wgrad_v2:           "
-              f"{t_w2*1e6:7.1f}us {flops/t_w2/1e12:6.1f}TF")
+        line = (f"[conv {tag}]   wgrad_v2:           "
+                f"{t_w2*1e6:7.1f}us {flops/t_w2/1e12:6.1f}TF")
+        if _v3_ok(C, F):
+            line += " | " + _wgrad_v3_column(ext, dy, x, flops)
+        print(line)
+
+
+HBM_BPS = 6.3e12   # what the hardware sustains (profiles/README.md)
+
+
+def _v3_ok(C, F):
+    return F % 8 == 0 and F <= 64 and (C % 8 == 0 or C in (1, 3))
+
+
+def _wgrad_v3_column(ext, dy, x, flops, t_w3=None):
+    """Whole tconv_wgrad_v3 call (first-layer channel pad included) beside
+    the whole v2 call: time, the call's byte floor (dY + X once at HBM
+    rate) and the share of it reached, and the results compared at the
+    size that is timed."""
+    if t_w3 is None:
+        t_w3 = timeit(lambda: ext.tconv_wgrad_v3(dy, x, 1, True))
+    floor = (dy.numel() + x.numel()) * 2 / HBM_BPS
+    dw2 = ext.tconv_wgrad_v2(dy, x, 1, True)[0]
+    dw3 = ext.tconv_wgrad_v3(dy, x, 1, True)[0]
+    return (f"wgrad_v3 {t_w3*1e6:7.1f}us {flops/t_w3/1e12:6.1f}TF "
+            f"floor {floor*1e6:6.1f}us (floor/time {100*floor/t_w3:4.1f}%) "
+            f"max|dw3-dw2| {(dw3 - dw2).abs().max().item():.3e} "
+            f"max|dw2| {dw2.abs().max().item():.3e}")
+
+
+def bench_wgrad(T, NB, H, W, C, F, tag):
+    """wgrad v1 / v2 / v3 whole calls at one shape, interleaved."""
+    dev = torch.device("cuda")
+    ext = hip_ext()
+    x = torch.randn(T, NB, H, W, C, device=dev).to(torch.bfloat16)
+    dy = torch.randn(T, NB, H, W, F, device=dev).to(torch.bfloat16)
+    flops = 2.0 * T * NB * H * W * F * 9 * C
+    fns = [lambda: ext.tconv_wgrad(dy, x, 1, True),
+           lambda: ext.tconv_wgrad_v2(dy, x, 1, True),
+           lambda: ext.tconv_wgrad_v3(dy, x, 1, True)]
+    # timed windows of some 20 ms of kernel work, whatever the shape
+    reps = max(3, min(100, int(0.02 / timeit(fns[2], reps=2, warmup=1))))
+    t1, t2, t3 = _median_rounds(fns, rounds=3, reps=reps, warmup=2)
+    print(f"[wgrad {tag}] T{T} NB{NB} {H}x{W} C{C}->F{F} K={NB*H*W} | "
+          f"v1 {t1*1e6:8.1f}us | v2 {t2*1e6:8.1f}us | "
+          + _wgrad_v3_column(ext, dy, x, flops, t3)
+          + f" | v3/v2 x{t2/t3:4.2f} v3/v1 x{t1/t3:4.2f}", flush=True)
+    del x, dy
+    torch.cuda.empty_cache()
+
+
+def main_wgrad():
+    for T in (128, 32):
+        # mini-imagenet 5w1s: target pass (75 images), then support (5)
+        bench_wgrad(T, 75, 84, 84, 3, 48, "mi-conv0-tgt")
+        bench_wgrad(T, 75, 42, 42, 48, 48, "mi-conv1-tgt")
+        bench_wgrad(T, 75, 21, 21, 48, 48, "mi-conv2-tgt")
+        bench_wgrad(T, 75, 10, 10, 48, 48, "mi-conv3-tgt")
+        bench_wgrad(T, 5, 84, 84, 3, 48, "mi-conv0-sup")
+        bench_wgrad(T, 5, 42, 42, 48, 48, "mi-conv1-sup")
+        bench_wgrad(T, 5, 21, 21, 48, 48, "mi-conv2-sup")
+        bench_wgrad(T, 5, 10, 10, 48, 48, "mi-conv3-sup")
+        # omniglot 20w5s: 100-image support and target passes
+        bench_wgrad(T, 100, 28, 28, 1, 64, "om-conv0-tgt")
+        bench_wgrad(T, 100, 14, 14, 64, 64, "om-conv1-tgt")
+        bench_wgrad(T, 100, 7, 7, 64, 64, "om-conv2-tgt")
+        bench_wgrad(T, 100, 3, 3, 64, 64, "om-conv3-tgt")
 
 
 def bench_bn(T, M, C, tag):
@@ -411,12 +477,16 @@ def main():
     if "--ln" in sys.argv or "--ln-model" in sys.argv:
         main_ln()
         return
+    if "--wgrad" in sys.argv:
+        main_wgrad()
+        return
     if "--strided" in sys.argv or "--strided-model" in sys.argv:
         # max_pooling=False backbone only: kernels vs the routing they replace
         main_strided("--strided-model" in sys.argv)
         return
     # mini-imagenet flagship: 8 tasks/GPU, target pass (75 imgs/task)
     bench_conv(8, 75, 84, 84, 3, 48, "mi-conv0-tgt")
+    bench_conv(128, 75, 84, 84, 3, 48, "mi-conv0-tgt-128")
     bench_conv(8, 75, 42, 42, 48, 48, "mi-conv1-tgt")
     bench_conv(8, 75, 21, 21, 48, 48, "mi-conv2-tgt")
     bench_conv(8, 5, 42, 42, 48, 48, "mi-conv1-sup")
