@@ -88,6 +88,150 @@ void dconv_fwd_kernel(const bf16* __restrict__ X, const float* __restrict__ W,
 }
 
 // ---------------------------------------------------------------------------
+// fwd v2 (default for the workloads' C in {1,3}): the same fp32 arithmetic
+// on the fp32 matrix unit.  v_mfma_f32_16x16x4_f32 runs at the VALU's peak
+// rate and is bit for bit a k-ordered fmaf chain on the accumulator, so
+//   acc = bias[f]; acc = fmaf(float(x), w_fp32, acc) over ky, kx, c
+// comes out as in dconv_fwd_kernel (an out-of-image tap contributes
+// fmaf(0, w, acc) instead of being skipped: at most the sign of a zero).
+// What changes is how the operands arrive:
+//   * weights sit in REGISTERS for the kernel's lifetime, one per lane per
+//     MFMA (A[f = lane&15][k = lane>>4]): no LDS at all.  The v1 kernel's
+//     wave-uniform ds_read_b128 costs 4 LDS cycles per 4 weights whatever
+//     the broadcast, 12 reads per 24 v_pk_fma_f32 — twice the FMA time on
+//     the CU's one LDS port — and its x loads are 9C dependent latencies;
+//   * x is one 2-byte load per lane per k-step (B[k = lane>>4][pos =
+//     lane&15]), all 9C/4 of a tile issued together and one tile ahead of
+//     the MFMAs that consume them;
+//   * D[f][pos] leaves each lane 4 consecutive f of one position: 8-byte
+//     stores, a tile's FT*32 bytes of Y contiguous.
+// k = (ky*3+kx)*CT + c is padded to a multiple of 4 with w = x = 0.
+// A wave owns 16-position tiles tile0, tile0+S, ... and advances its
+// (img, ho, wo) by S tiles with adds and compares.
+// ---------------------------------------------------------------------------
+typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
+typedef __attribute__((__vector_size__(4 * sizeof(short)))) short bf16x4;
+
+template <int FT, int CT>
+__global__ __launch_bounds__(256)
+void dconv_fwd_v2_kernel(const bf16* __restrict__ X, const float* __restrict__ W,
+                         const float* __restrict__ bias, bf16* __restrict__ Y,
+                         int NB, int H, int Wd, int Ho, int Wo, int pad) {
+  constexpr int K = 9 * CT;
+  constexpr int KS = (K + 3) / 4;    // MFMA k-steps
+  constexpr int NT = FT / 16;        // 16-channel tiles
+  constexpr int kInvalid = -(1 << 30);
+  const int t = blockIdx.y;
+  // wave-uniform by construction: keeps the tile loop on the scalar unit
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int lane = threadIdx.x % WAVE;
+  const int li = lane & 15;          // A: channel in tile; B, D: position in tile
+  const int g = lane >> 4;           // A, B: k in step; D: 4-channel group
+  const int Mtot = NB * Ho * Wo;
+  const int ntiles = (Mtot + 15) / 16;
+
+  const float* Wt = W + (long)t * FT * CT * 9;
+  const unsigned short* Xt =
+      (const unsigned short*)X + (long)t * NB * H * Wd * CT;
+  short* Yt = (short*)Y + (long)t * Mtot * FT;
+
+  // per-lane k decode (once): weight registers, x tap offsets
+  float wa[KS][NT];
+  int koff[KS], kdy[KS], kdx[KS];
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    const int k = 4 * s + g;
+    const bool kv = k < K;
+    const int tap = kv ? k / CT : 0;
+    const int c = kv ? k - tap * CT : 0;
+    const int dy = tap / 3, dx = tap - dy * 3;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+      wa[s][nt] = kv ? Wt[((nt * 16 + li) * CT + c) * 9 + tap] : 0.f;
+    koff[s] = (dy * Wd + dx) * CT + c;
+    kdy[s] = kv ? dy : (1 << 20);    // k padding: no row is ever in range
+    kdx[s] = dx;
+  }
+  f32x4 bv[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      bv[nt][j] = bias ? bias[(long)t * FT + nt * 16 + g * 4 + j] : 0.f;
+
+  // this lane's position m = tile*16 + li and its stride per iteration
+  const int stride = gridDim.x * (blockDim.x / WAVE);   // tiles
+  const int dm = stride * 16;
+  const int dwo = dm % Wo;
+  const int dho = (dm / Wo) % Ho;
+  const int dimg = (dm / Wo) / Ho;
+  int tile = blockIdx.x * (blockDim.x / WAVE) + wave;
+  int m = tile * 16 + li;
+  int wo = m % Wo, ho = (m / Wo) % Ho, img = (m / Wo) / Ho;
+
+  // the 9C (padded) window values of position (img, ho, wo), raw bf16;
+  // every load is independent of the others
+  unsigned short xr[KS];
+#define DFWD2_LOAD()                                                           \
+  do {                                                                         \
+    const bool mv = m < Mtot;                                                  \
+    const int hb = mv ? ho - pad : kInvalid;                                   \
+    const int wb = wo - pad;                                                   \
+    const int base = mv ? ((img * H + hb) * Wd + wb) * CT : 0;                 \
+    _Pragma("unroll")                                                          \
+    for (int s = 0; s < KS; ++s) {                                             \
+      const bool ok = (unsigned)(hb + kdy[s]) < (unsigned)H &&                 \
+                      (unsigned)(wb + kdx[s]) < (unsigned)Wd;                  \
+      xr[s] = ok ? Xt[base + koff[s]] : (unsigned short)0;                     \
+    }                                                                          \
+  } while (0)
+
+  // Per iteration: convert the window loaded one iteration ago, issue the
+  // next tile's loads, then the MFMAs and the stores — the loads are in
+  // flight behind the MFMA run.  (Measured slower, 3.5 against 2.9 ms at the
+  // flagship's target call: branch-free clamped loads all issued ahead of
+  // the MFMAs and consumed before the stores, so that the in-order memory
+  // counter never waits on stores just issued.)
+  DFWD2_LOAD();
+  for (; tile < ntiles; tile += stride) {
+    float xb[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+      xb[s] = __uint_as_float((unsigned)xr[s] << 16);
+    const int m_cur = m;
+    // next tile's position (past the end: every load predicated off)
+    m += dm;
+    wo += dwo;
+    if (wo >= Wo) { wo -= Wo; ho += 1; }
+    ho += dho;
+    if (ho >= Ho) { ho -= Ho; img += 1; }
+    img += dimg;
+    DFWD2_LOAD();
+
+    f32x4 acc[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[nt] = bv[nt];
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[s][nt], xb[s],
+                                                       acc[nt], 0, 0, 0);
+    if (m_cur < Mtot) {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        bf16x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          v[j] = (short)__bfloat16_as_short(__float2bfloat16(acc[nt][j]));
+        *(bf16x4*)&Yt[(long)m_cur * FT + nt * 16 + g * 4] = v;
+      }
+    }
+  }
+#undef DFWD2_LOAD
+}
+
+// ---------------------------------------------------------------------------
 // wgrad: dWacc [T, nsl, 9C, F] (+ dBacc [T, nsl, F]) — same accumulator
 // layout as the GEMM wgrad so the shared finalize kernel applies.
 // lane = f; wave walks contiguous positions; CT = compile-time C.
@@ -234,9 +378,44 @@ torch::Tensor dconv_fwd(torch::Tensor x, torch::Tensor w,
     bptr = bc.data_ptr<float>();
   }
   const long Mtot = (long)NB * Ho * Wo;
-  const int blocks = (int)std::min<long>((Mtot + 255) / 256, 4096);
   auto stream = at::cuda::getCurrentCUDAStream();
-#define LAUNCH_DFWD(FT)                                                        \
+  // v2 (fp32 MFMA, weights in registers) for the workloads' C in {1, 3};
+  // MAML355_DCONV_FWD_V2=0 restores dconv_fwd_kernel everywhere
+  const char* v2_env = getenv("MAML355_DCONV_FWD_V2");
+  const bool v2 = (C == 1 || C == 3) && !(v2_env && v2_env[0] == '0');
+  if (v2) {
+    TORCH_CHECK(Ho == H + 2 * pad - 2 && Wo == W + 2 * pad - 2 && Ho >= 1 &&
+                    Wo >= 1 && pad >= 0,
+                "dconv_fwd: Ho/Wo do not match a stride-1 3x3 conv");
+    // positions and element offsets within a task are 32-bit in the kernel
+    TORCH_CHECK(Mtot < (1L << 30) && (long)NB * H * W * C < (1L << 30),
+                "dconv_fwd: task too large for 32-bit offsets");
+    // 4 waves per block, ~8 tiles of 16 positions per wave: the per-wave
+    // weight load (9C/4 * F/16 registers) is amortised, the grid stays wide
+    const long ntiles = (Mtot + 15) / 16;
+    const int blocks2 =
+        (int)std::max<long>(1, std::min<long>((ntiles + 31) / 32, 2048));
+#define LAUNCH_DFWD2(FT, CT)                                                   \
+  hipLaunchKernelGGL((dconv_fwd_v2_kernel<FT, CT>), dim3(blocks2, T),          \
+                     dim3(256), 0, stream.stream(),                            \
+                     reinterpret_cast<const bf16*>(x.data_ptr()),              \
+                     wc.data_ptr<float>(), bptr,                               \
+                     reinterpret_cast<bf16*>(y.data_ptr()),                    \
+                     NB, H, W, (int)Ho, (int)Wo, (int)pad)
+#define LAUNCH_DFWD2_C(FT)                                                     \
+  do { if (C == 1) LAUNCH_DFWD2(FT, 1); else LAUNCH_DFWD2(FT, 3); } while (0)
+    switch (F) {
+      case 16: LAUNCH_DFWD2_C(16); break;
+      case 32: LAUNCH_DFWD2_C(32); break;
+      case 48: LAUNCH_DFWD2_C(48); break;
+      default: LAUNCH_DFWD2_C(64); break;
+    }
+#undef LAUNCH_DFWD2_C
+#undef LAUNCH_DFWD2
+    return y;
+  }
+  const int blocks = (int)std::min<long>((Mtot + 255) / 256, 4096);
+#define LAUNCH_DFWD(FT)                                                       \
   hipLaunchKernelGGL((dconv_fwd_kernel<FT>), dim3(blocks, T), dim3(256), 0,    \
                      stream.stream(),                                          \
                      reinterpret_cast<const bf16*>(x.data_ptr()),              \

@@ -22,8 +22,8 @@
 //   v1: synchronous register staging between two barriers (im2col gather
 //       + transposed B writes) — the fallback for Ci % 8 != 0.
 //   v2 (default, single-buffer): `global_load_lds` async DMA staging with
-//       a padded input (no boundary predicates), a pre-swizzled weight
-//       LDS image, per-thread incremental k-state and a zero page for the
+//       the unpadded input, a pre-swizzled weight LDS image, per-thread
+//       incremental k-state and a zero page for the border taps and the
 //       tails.  Measured: conv1 192->222 TF, omiglot conv1 289->312; the
 //       double-buffered 2-phase variant (MAML355_CONV_V2_SBUF=0) LOSES
 //       through occupancy (80 KB LDS -> 2 blocks/CU).
@@ -32,6 +32,7 @@
 // via LDS-occupancy / issue-pressure cliffs; r2: the pipeline ladder).
 
 #include "common.h"
+#include "tconv_mm_addr.h"
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -326,8 +327,12 @@ void tconv_mm_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wp,
 //             barrier (drains vmcnt -> next tile ready); buf ^= 1
 //
 // Enablers (all pre-computed on the host side):
-//   * input is PADDED ([T,NB,H+2p,W+2p,Ci]) so every im2col address is
-//     valid -> no boundary predicates, per-lane source addresses only
+//   * input is read as stored, UNPADDED: a staging slot is 8 channels of
+//     one (dy,dx) tap, so one border test per slot and K-step picks the
+//     tensor address or the zero page (tconv_mm_addr.h, walked on the CPU
+//     by tests/host/tconv_mm_addr_check.cpp).  MAML355_CONV_V2_NOPAD=0
+//     feeds the same kernel a zero-bordered copy with pad = 0 instead —
+//     the earlier scheme, one extra pass over the input per call
 //   * weights are repacked into the exact swizzled LDS image
 //     ([T,ksteps,64,BK] with the XOR swizzle pre-applied and zeros in
 //     the K/Co tails) -> B staging is a linear byte copy
@@ -335,7 +340,8 @@ void tconv_mm_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wp,
 //     ERRATA 21: global_load_lds writes linearly, so the swizzle must
 //     live in the source address; the ds_read side applies the same
 //     involution)
-//   * K-tail / M-tail lanes read a 16B zero page instead of predicating
+//   * border / K-tail / M-tail lanes read a 16B zero page instead of
+//     predicating the load
 // Requires Ci % 8 == 0 (the first conv layer's C in {1,3} keeps v1).
 // LDS: 2x(256x64) A + 2x(64x64) B bf16 = 80 KB dynamic -> 2 blocks/CU.
 // ---------------------------------------------------------------------------
@@ -348,13 +354,14 @@ void tconv_mm_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wp,
 // VALU register staging).
 template <bool DBUF>
 __global__ __launch_bounds__(512, 2)
-void tconv_mm_v2_kernel(const bf16* __restrict__ Xp, const bf16* __restrict__ Wimg,
+void tconv_mm_v2_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wimg,
                         const float* __restrict__ bias, const bf16* __restrict__ zpage,
                         bf16* __restrict__ Y, float* __restrict__ sums_out,
-                        int T, int NB, int Hp, int Wp, int Ci,
-                        int Ho, int Wo, int Co) {
+                        int T, int NB, int H, int W, int Ci,
+                        int Ho, int Wo, int Co, int pad) {
   const int t = blockIdx.y;
-  const long Mtot = (long)NB * Ho * Wo;
+  const tcmm::Geom g = tcmm::make_geom(NB, H, W, Ci, Ho, Wo, pad);
+  const long Mtot = g.Mtot;
   const long m0 = (long)blockIdx.x * BM;
   const int K9 = 9 * Ci;
   const int ksteps = (K9 + BK - 1) / BK;
@@ -366,7 +373,7 @@ void tconv_mm_v2_kernel(const bf16* __restrict__ Xp, const bf16* __restrict__ Wi
 #define LDS_B(buf_) \
   (smem + (DBUF ? 2 : 1) * (BM * BK) + (DBUF ? (buf_) * (64 * BK) : 0))
 
-  const bf16* Xt = Xp + (long)t * NB * Hp * Wp * Ci;
+  const bf16* Xt = X + (long)t * NB * H * W * Ci;
   const short* Wt = (const short*)Wimg + (long)t * ksteps * 64 * BK;
 
   const int wave = threadIdx.x / WAVE;
@@ -374,55 +381,28 @@ void tconv_mm_v2_kernel(const bf16* __restrict__ Xp, const bf16* __restrict__ Wi
   const int fr = lane & 15;
   const int fk = lane >> 4;
 
-  // loop-invariant per-thread A-staging descriptors: 4 slots of 16B; slot
-  // s -> (row m = s>>3, dest 8-col group j = s&7); source col group is
-  // j ^ (m&7) (inverse swizzle on the source side).  The k -> (dy,dx,c)
-  // decomposition advances INCREMENTALLY per K-step (adds + compares,
-  // no division in the loop).
-  int a_rb[4];   // element offset of (n, ho, wo) in the padded input, or -1
-  int a_c[4], a_dy[4], a_dx[4], a_koff[4], a_k[4];
+  // loop-invariant per-thread A-staging descriptors (tconv_mm_addr.h): 4
+  // slots of 16B, slot s -> (row m = s>>3, dest 8-col group j = s&7); the
+  // source col group is j ^ (m&7) (inverse swizzle on the source side).  The
+  // four slots sit 64 rows apart and share one k -> (dy,dx,c) state, which
+  // advances INCREMENTALLY per K-step (adds + compares, no division in the
+  // loop); per slot there is the row base and (ho-pad, wo-pad) for the
+  // border test.
+  tcmm::KState a_k = tcmm::k_init(g, tcmm::slot_k8(threadIdx.x));
+  tcmm::Row a_row[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int s = q * 512 + threadIdx.x;
-    const int m = s >> 3;
-    const int k8 = ((s & 7) ^ (m & 7)) * 8;   // k base within the K-step
-    a_k[q] = k8;
-    const int kyx = k8 / Ci;
-    a_c[q] = k8 - kyx * Ci;
-    a_dy[q] = kyx / 3;
-    a_dx[q] = kyx % 3;
-    a_koff[q] = (a_dy[q] * Wp + a_dx[q]) * Ci + a_c[q];
-    const long mg = m0 + m;
-    if (mg < Mtot) {
-      const int wo = (int)(mg % Wo);
-      const int ho = (int)((mg / Wo) % Ho);
-      const int n = (int)(mg / ((long)Wo * Ho));
-      a_rb[q] = ((n * Hp + ho) * Wp + wo) * Ci;
-    } else {
-      a_rb[q] = -1;
-    }
+    a_row[q] = tcmm::row_init(g, m0 + tcmm::slot_row(q * 512 + threadIdx.x));
   }
-#define V2_ADVANCE()                                                           \
-  do {                                                                         \
-    _Pragma("unroll")                                                          \
-    for (int q = 0; q < 4; ++q) {                                              \
-      a_k[q] += BK;                                                            \
-      a_c[q] += BK;                                                            \
-      while (a_c[q] >= Ci) {                                                   \
-        a_c[q] -= Ci;                                                          \
-        if (++a_dx[q] == 3) { a_dx[q] = 0; ++a_dy[q]; }                        \
-      }                                                                        \
-      a_koff[q] = (a_dy[q] * Wp + a_dx[q]) * Ci + a_c[q];                      \
-    }                                                                          \
-  } while (0)
+#define V2_ADVANCE() tcmm::k_advance(g, a_k)
 
 #define V2_STAGE(ks_, buf_)                                                    \
   do {                                                                         \
     _Pragma("unroll")                                                          \
     for (int q = 0; q < 4; ++q) {                                              \
-      const bf16* src = (a_rb[q] < 0 || a_k[q] >= K9)                          \
-                            ? zpage                                            \
-                            : Xt + a_rb[q] + a_koff[q];                        \
+      int off;                                                                 \
+      const bf16* src = tcmm::slot_src(g, a_row[q], a_k, off) ? Xt + off       \
+                                                              : zpage;         \
       auto ldst = (__attribute__((address_space(3))) void*)(                   \
           &LDS_A(buf_)[((long)q * 512 + wave * 64) * 8]);                      \
       __builtin_amdgcn_global_load_lds(                                        \
@@ -1123,6 +1103,18 @@ int ew_grid2(long total, int threads) {
   long blocks = (total + threads - 1) / threads;
   return (int)std::min<long>(blocks, 4096);
 }
+
+// 16-byte-aligned zeros that tail and border lanes of the async staging read
+// instead of predicating: one page per device, allocated and filled once (a
+// torch::zeros per call is a fill-kernel launch per call).
+const bf16* conv_zero_page(const torch::Tensor& like) {
+  static auto* pages = new std::vector<torch::Tensor>(64);
+  const int dev = like.get_device();
+  TORCH_CHECK(dev >= 0 && dev < 64);
+  auto& p = (*pages)[dev];
+  if (!p.defined()) p = torch::zeros({128}, like.options());
+  return reinterpret_cast<const bf16*>(p.data_ptr());
+}
 }  // namespace
 
 torch::Tensor tconv_repack(torch::Tensor w, bool dgrad) {
@@ -1202,11 +1194,22 @@ std::vector<torch::Tensor> tconv_mm_v2(torch::Tensor x, torch::Tensor wimg,
   const int T = (int)x.size(0), NB = (int)x.size(1), H = (int)x.size(2),
             W = (int)x.size(3), Ci = (int)x.size(4);
   TORCH_CHECK(Ci % 8 == 0 && Co <= 64);
+  TORCH_CHECK(pad >= 0 && pad <= 2 && Ho == H + 2 * pad - 2 &&
+              Wo == W + 2 * pad - 2 && Ho >= 1 && Wo >= 1,
+              "tconv_mm_v2: Ho/Wo do not match a stride-1 3x3 conv");
+  // slot offsets within a task are 32-bit (tconv_mm_addr.h)
+  TORCH_CHECK((long)NB * (H + 4) * (W + 4) * Ci < (1L << 31),
+              "tconv_mm_v2: task too large for 32-bit offsets");
   auto stream = at::cuda::getCurrentCUDAStream();
-  // pad (p == 0 -> use x directly: every im2col address is already valid)
+  // default: the kernel reads x as stored and tests the border per slot.
+  // MAML355_CONV_V2_NOPAD=0: zero-bordered copy first, then the kernel runs
+  // on it with pad 0 (every tap in range).
+  const char* nopad_env = getenv("MAML355_CONV_V2_NOPAD");
+  const bool nopad = !(nopad_env && nopad_env[0] == '0');
   torch::Tensor xp = x;
-  int Hp = H, Wp = W;
-  if (pad > 0) {
+  int Hp = H, Wp = W, kpad = (int)pad;
+  if (!nopad && pad > 0) {
+    kpad = 0;
     Hp = H + 2 * (int)pad;
     Wp = W + 2 * (int)pad;
     xp = torch::empty({T, NB, Hp, Wp, Ci}, x.options());
@@ -1221,7 +1224,13 @@ std::vector<torch::Tensor> tconv_mm_v2(torch::Tensor x, torch::Tensor wimg,
   auto sums = with_stats
                   ? torch::zeros({T, 2, Co}, x.options().dtype(torch::kFloat32))
                   : torch::empty({0}, x.options().dtype(torch::kFloat32));
-  auto zpage_cache = torch::zeros({16}, x.options());
+  // the restored path keeps its per-call page too, so an A/B of the toggle
+  // compares whole calls as they were
+  torch::Tensor zpage_call;
+  if (!nopad) zpage_call = torch::zeros({16}, x.options());
+  const bf16* zpage =
+      nopad ? conv_zero_page(x)
+            : reinterpret_cast<const bf16*>(zpage_call.data_ptr());
   const float* bptr = nullptr;
   torch::Tensor bc;
   if (bias.has_value()) {
@@ -1249,10 +1258,9 @@ std::vector<torch::Tensor> tconv_mm_v2(torch::Tensor x, torch::Tensor wimg,
                      stream.stream(),                                          \
                      reinterpret_cast<const bf16*>(xp.data_ptr()),             \
                      reinterpret_cast<const bf16*>(wimg.data_ptr()), bptr,     \
-                     reinterpret_cast<const bf16*>(zpage_cache.data_ptr()),    \
-                     reinterpret_cast<bf16*>(y.data_ptr()),                    \
+                     zpage, reinterpret_cast<bf16*>(y.data_ptr()),             \
                      with_stats ? sums.data_ptr<float>() : nullptr,            \
-                     T, NB, Hp, Wp, Ci, (int)Ho, (int)Wo, (int)Co)
+                     T, NB, Hp, Wp, Ci, (int)Ho, (int)Wo, (int)Co, kpad)
   if (sbuf) LAUNCH_MMV2(false, V2_LDS_BYTES_SBUF);
   else LAUNCH_MMV2(true, V2_LDS_BYTES);
 #undef LAUNCH_MMV2
@@ -1361,7 +1369,7 @@ std::vector<torch::Tensor> tconv_wgrad_v2(torch::Tensor dy, torch::Tensor x,
                        reinterpret_cast<bf16*>(xt.data_ptr()),
                        T, NB, H, W, C, Hxp, Wxp, (int)pad);
   }
-  auto zpage = torch::zeros({16}, x.options());
+  const bf16* zpage = conv_zero_page(x);
 
   // n-columns per block: NSUB=2 (128 cols, 2x MFMA per barrier) pays only
   // on large-K shapes (measured: conv1-tgt 94->104 TF; SLOWER below
@@ -1391,8 +1399,7 @@ std::vector<torch::Tensor> tconv_wgrad_v2(torch::Tensor dy, torch::Tensor x,
   hipLaunchKernelGGL((tconv_wgrad_v2_kernel<NS_, DET_>), grid, dim3(256), 0,   \
                      stream.stream(),                                          \
                      reinterpret_cast<const bf16*>(dyt.data_ptr()),            \
-                     reinterpret_cast<const bf16*>(xt.data_ptr()),             \
-                     reinterpret_cast<const bf16*>(zpage.data_ptr()),          \
+                     reinterpret_cast<const bf16*>(xt.data_ptr()), zpage,      \
                      acc.data_ptr<float>(),                                    \
                      with_bias ? dbacc.data_ptr<float>() : nullptr,            \
                      T, NB, Ho, Wo8, Hxp, Wxp, C, F, Kr, Kprime, (int)kchunk)

@@ -6,6 +6,7 @@
     python tools/bench_kernels.py --ln              # layer-norm kernels vs torch
     python tools/bench_kernels.py --ln-model        # ... plus whole-model A/B
     python tools/bench_kernels.py --wgrad           # wgrad v1 / v2 / v3 per shape
+    python tools/bench_kernels.py --conv-input      # pad copy / first-layer fwd A/B
 
 Prints per-kernel time, effective TFLOP/s (conv) or TB/s (memory-bound),
 so optimization effort goes where the roofline says.
@@ -128,6 +129,101 @@ def main_wgrad():
         bench_wgrad(T, 100, 14, 14, 64, 64, "om-conv1-tgt")
         bench_wgrad(T, 100, 7, 7, 64, 64, "om-conv2-tgt")
         bench_wgrad(T, 100, 3, 3, 64, 64, "om-conv3-tgt")
+
+
+PEAK_F32 = 157.3e12   # fp32 vector / fp32 MFMA peak (FLOP/s)
+
+
+def _with_env(name, value, fn):
+    """fn under one setting of a per-call toggle (None = unset, the default)."""
+    import os
+
+    def run():
+        if value is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = value
+        try:
+            return fn()
+        finally:
+            os.environ.pop(name, None)
+    return run
+
+
+def _reps_for(fn, window=0.02):
+    return max(3, min(100, int(window / timeit(fn, reps=2, warmup=1))))
+
+
+def bench_conv_input(T, NB, H, W, C, tag):
+    """tconv_mm_v2 whole calls, forward and dgrad (C -> C, pad 1): zero-
+    bordered copy + GEMM (MAML355_CONV_V2_NOPAD=0) against the GEMM reading
+    the unpadded input, interleaved; results compared at the timed size."""
+    dev = torch.device("cuda")
+    ext = hip_ext()
+    x = torch.randn(T, NB, H, W, C, device=dev).to(torch.bfloat16)
+    w = torch.randn(T, C, C, 3, 3, device=dev).mul(0.1)
+    b = torch.randn(T, C, device=dev)
+    wp = ext.tconv_repack_v2(w, False)
+    wpd = ext.tconv_repack_v2(w, True)
+    flops = 2.0 * T * NB * H * W * C * 9 * C
+    cols = []
+    for name, call in (
+            ("fwd", lambda: ext.tconv_mm_v2(x, wp, b, 1, H, W, C, False)[0]),
+            ("dgrad", lambda: ext.tconv_mm_v2(x, wpd, None, 1, H, W, C, False)[0])):
+        off = _with_env("MAML355_CONV_V2_NOPAD", "0", call)
+        on = _with_env("MAML355_CONV_V2_NOPAD", None, call)
+        same = torch.equal(off(), on())
+        t0, t1 = _median_rounds([off, on], rounds=3, reps=_reps_for(on), warmup=2)
+        cols.append(f"{name} pad+mm {t0*1e6:8.1f}us | mm {t1*1e6:8.1f}us "
+                    f"{flops/t1/1e12:6.1f}TF x{t0/t1:4.2f} "
+                    f"{'bitwise' if same else 'DIFFERENT'}")
+    print(f"[conv-input {tag}] T{T} NB{NB} {H}x{W} C{C} | " + " | ".join(cols),
+          flush=True)
+    del x, w, wp, wpd
+    torch.cuda.empty_cache()
+
+
+def bench_dconv_fwd(T, NB, H, W, C, F, tag):
+    """First-layer forward: vector-unit kernel (MAML355_DCONV_FWD_V2=0)
+    against the fp32-MFMA kernel, with the store floor (Y bytes at the HBM
+    rate) and the FMA floor (flops at the fp32 peak) beside them."""
+    dev = torch.device("cuda")
+    ext = hip_ext()
+    x = torch.randn(T, NB, H, W, C, device=dev).to(torch.bfloat16)
+    w = torch.randn(T, F, C, 3, 3, device=dev).mul(0.1)
+    b = torch.randn(T, F, device=dev)
+    call = lambda: ext.dconv_fwd(x, w, b, 1, H, W)  # noqa: E731
+    off = _with_env("MAML355_DCONV_FWD_V2", "0", call)
+    on = _with_env("MAML355_DCONV_FWD_V2", None, call)
+    same = torch.equal(off(), on())
+    t0, t1 = _median_rounds([off, on], rounds=3, reps=_reps_for(on), warmup=2)
+    flops = 2.0 * T * NB * H * W * F * 9 * C
+    st_floor = T * NB * H * W * F * 2 / HBM_BPS
+    fma_floor = flops / PEAK_F32
+    print(f"[dconv-fwd {tag}] T{T} NB{NB} {H}x{W} C{C}->F{F} | "
+          f"old {t0*1e6:8.1f}us {flops/t0/1e12:5.1f}TF | "
+          f"new {t1*1e6:8.1f}us {flops/t1/1e12:5.1f}TF x{t0/t1:4.2f} | "
+          f"store floor {st_floor*1e6:7.1f}us FMA floor {fma_floor*1e6:7.1f}us "
+          f"(new/max floor x{t1/max(st_floor, fma_floor):4.2f}) | "
+          f"{'equal' if same else 'DIFFERENT'}", flush=True)
+    del x, w
+    torch.cuda.empty_cache()
+
+
+def main_conv_input():
+    for T in (128, 32):
+        # mini-imagenet 5w1s conv layers 1-3: target (75 images), support (5)
+        for nb, who in ((75, "tgt"), (5, "sup")):
+            bench_conv_input(T, nb, 42, 42, 48, f"mi-conv1-{who}")
+            bench_conv_input(T, nb, 21, 21, 48, f"mi-conv2-{who}")
+            bench_conv_input(T, nb, 10, 10, 48, f"mi-conv3-{who}")
+        # omniglot 20w5s: 100-image support and target passes
+        bench_conv_input(T, 100, 14, 14, 64, "om-conv1")
+        bench_conv_input(T, 100, 7, 7, 64, "om-conv2")
+        bench_conv_input(T, 100, 3, 3, 64, "om-conv3")
+        bench_dconv_fwd(T, 75, 84, 84, 3, 48, "mi-conv0-tgt")
+        bench_dconv_fwd(T, 5, 84, 84, 3, 48, "mi-conv0-sup")
+        bench_dconv_fwd(T, 100, 28, 28, 1, 64, "om-conv0")
 
 
 def bench_bn(T, M, C, tag):
@@ -479,6 +575,9 @@ def main():
         return
     if "--wgrad" in sys.argv:
         main_wgrad()
+        return
+    if "--conv-input" in sys.argv:
+        main_conv_input()
         return
     if "--strided" in sys.argv or "--strided-model" in sys.argv:
         # max_pooling=False backbone only: kernels vs the routing they replace
