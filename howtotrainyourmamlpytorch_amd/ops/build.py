@@ -30,6 +30,7 @@ SOURCES = [
     os.path.join(HIP_DIR, "sconv.hip"),
     os.path.join(HIP_DIR, "gavgpool.hip"),
     os.path.join(HIP_DIR, "layernorm.hip"),
+    os.path.join(HIP_DIR, "fconv.hip"),
 ]
 
 

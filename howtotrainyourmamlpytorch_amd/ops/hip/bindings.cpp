@@ -84,6 +84,13 @@ torch::Tensor sconv_dgrad(torch::Tensor dy, torch::Tensor wp, long pad,
                           long H, long W);
 std::vector<torch::Tensor> sconv_wgrad(torch::Tensor dy, torch::Tensor x,
                                        long pad, bool with_bias);
+// fconv.hip
+torch::Tensor fconv_repack(torch::Tensor w, bool dgrad);
+torch::Tensor fconv_mm(torch::Tensor x, torch::Tensor wp,
+                       c10::optional<torch::Tensor> bias, long pad,
+                       long Ho, long Wo);
+std::vector<torch::Tensor> fconv_wgrad(torch::Tensor dy, torch::Tensor x,
+                                       long pad, bool with_bias);
 // gavgpool.hip
 torch::Tensor gavgpool_fwd(torch::Tensor x);
 torch::Tensor gavgpool_bwd(torch::Tensor dy, long H, long W);
@@ -134,6 +141,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sconv_dgrad", &sconv_dgrad,
         "stride-2 3x3 conv input-grad (four parity sub-GEMMs)");
   m.def("sconv_wgrad", &sconv_wgrad, "stride-2 3x3 conv weight/bias grads");
+  m.def("fconv_repack", &fconv_repack,
+        "repack fp32 conv weights for the fp32 MFMA kernel (fwd/dgrad)");
+  m.def("fconv_mm", &fconv_mm, "task-batched fp32 MFMA 3x3 conv fwd/dgrad");
+  m.def("fconv_wgrad", &fconv_wgrad,
+        "task-batched fp32 MFMA 3x3 conv weight/bias grads (ordered split-K)");
   m.def("gavgpool_fwd", &gavgpool_fwd, "NHWC global average pool fwd");
   m.def("gavgpool_bwd", &gavgpool_bwd, "NHWC global average pool bwd");
   m.def("adam_step",&adam_step, "fused multi-tensor Adam + grad clamp");

@@ -20,8 +20,15 @@ through the inner-loop support forward):
   backward itself is not being differentiated, and composes the
   individual Functions under create_graph.
 
+fp32 activations (``--compute_dtype fp32``, ``--fp32_support_pass``): the
+stride-1 conv trio runs on fconv.hip (exact fp32 MFMA, unrounded weights,
+ordered split-K wgrad) and the linear head on linear.hip's fp32
+instantiation, composed like their bf16 twins.  ``MAML355_FCONV=0``
+restores the grouped-ATen conv and ``torch.bmm`` for A/B runs.
+
 Convs with a stride other than 1 or 2, more than 64 channels, or fp32
-compute fall back to the grouped-ATen composition, with a warning.
+compute at stride 2 fall back to the grouped-ATen composition, with a
+warning.
 """
 
 from __future__ import annotations
@@ -602,6 +609,97 @@ class _SConvWgradFn(torch.autograd.Function):
         return d_dy, d_x, None, None
 
 
+# ---------------------------------------------------------------------------
+# fp32 stride-1 conv trio — fconv.hip.  Composed exactly like the bf16 trio
+# above: mutually bilinear, each backward calls the other two, the fused db
+# carries its second-order term.  Weights are used unrounded; C and F are
+# any value in 1..64 (no channel padding); wgrad is always the ordered
+# private-slice reduction, so the trio is bitwise reproducible in every mode.
+# ---------------------------------------------------------------------------
+def _fconv_on() -> bool:
+    """MAML355_FCONV=0 restores the pre-kernel fp32 behaviour (grouped-ATen
+    conv, torch.bmm linear head) for A/B runs."""
+    return os.environ.get("MAML355_FCONV", "1") != "0"
+
+
+class _FConvFwdFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, pad):
+        ctx.save_for_backward(x, w)
+        ctx.pad = pad
+        ctx.has_bias = b is not None
+        H, W = x.shape[2], x.shape[3]
+        wp = _ext().fconv_repack(w, False)
+        return _ext().fconv_mm(x, wp, b, pad, H + 2 * pad - 2, W + 2 * pad - 2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = _FConvDgradFn.apply(dy, w, ctx.pad)
+        if ctx.needs_input_grad[1]:
+            want_bias = ctx.has_bias and ctx.needs_input_grad[2]
+            dw, db = _FConvWgradFn.apply(dy, x, ctx.pad, want_bias)
+            if not want_bias:
+                db = None
+        elif ctx.has_bias and ctx.needs_input_grad[2]:
+            db = dy.sum(dim=(1, 2, 3))
+        return dx, dw, db, None
+
+
+class _FConvDgradFn(torch.autograd.Function):
+    """dx = dgrad(dy, w): fconv_mm with flipped/transposed repacked weights
+    and pad' = 2 - pad."""
+
+    @staticmethod
+    def forward(ctx, dy, w, pad):
+        ctx.save_for_backward(dy, w)
+        ctx.pad = pad
+        Ho, Wo = dy.shape[2], dy.shape[3]
+        wp = _ext().fconv_repack(w, True)
+        return _ext().fconv_mm(dy, wp, None, 2 - pad,
+                               Ho - 2 * pad + 2, Wo - 2 * pad + 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        dy, w = ctx.saved_tensors
+        g = g.contiguous()
+        d_dy = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_dy = _FConvFwdFn.apply(g, w, None, ctx.pad)
+        if ctx.needs_input_grad[1]:
+            d_w = _FConvWgradFn.apply(dy, g, ctx.pad, False)[0]
+        return d_dy, d_w, None
+
+
+class _FConvWgradFn(torch.autograd.Function):
+    """(dy, x) -> (dw, db) with the bias gradient fused, as _ConvWgradFn."""
+
+    @staticmethod
+    def forward(ctx, dy, x, pad, with_bias):
+        ctx.save_for_backward(dy, x)
+        ctx.pad = pad
+        dw, db = _ext().fconv_wgrad(dy, x, pad, with_bias)
+        return dw, db
+
+    @staticmethod
+    def backward(ctx, gw, gdb):
+        dy, x = ctx.saved_tensors
+        d_dy = d_x = None
+        if ctx.needs_input_grad[0]:
+            if gw is not None:
+                d_dy = _FConvFwdFn.apply(x, gw.contiguous(), None, ctx.pad)
+            if gdb is not None:
+                T, F = gdb.shape
+                add = gdb.view(T, 1, 1, 1, F).to(dy.dtype)
+                d_dy = add.expand_as(dy).contiguous() if d_dy is None else d_dy + add
+        if ctx.needs_input_grad[1] and gw is not None:
+            d_x = _FConvDgradFn.apply(dy, gw.contiguous(), ctx.pad)
+        return d_dy, d_x, None, None
+
+
 _FALLBACK_WARNED = set()
 
 
@@ -617,6 +715,17 @@ def _warn_fallback(reason: str) -> None:
 
 def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
     # w is task-batched [T, F, C, 3, 3]: dim 1 = out-channels, dim 2 = in
+    if (x.dtype == torch.float32 and stride == 1 and padding in (0, 1)
+            and w.shape[1] <= 64 and w.shape[2] <= 64 and _fconv_on()):
+        # fp32 activations: the fp32 MFMA trio, weights and bias unrounded.
+        # No BN-stats epilogue: return_stats yields empty sums and the BN
+        # kernels compute their own statistics, as on the stride-2 path.
+        y = _FConvFwdFn.apply(x.contiguous(), w.float().contiguous(),
+                              b.float().contiguous() if b is not None else None,
+                              padding)
+        if return_stats:
+            return y, torch.empty(0, device=x.device, dtype=torch.float32)
+        return y
     strided_ok = stride == 2 and padding in (0, 1)
     if (not (stride == 1 or strided_ok) or x.dtype != torch.bfloat16
             or w.shape[1] > 64 or w.shape[2] > 64):
@@ -731,8 +840,11 @@ class _LinWgradFn(torch.autograd.Function):
 
 
 def task_linear(x, w, b=None):
+    if x.dtype == torch.float32 and _fconv_on():
+        # fp32 activations: the same kernel trio, w/b unrounded, fp32 out
+        return _LinFwdFn.apply(x.contiguous(), w, b)
     if x.dtype != torch.bfloat16:
-        # fp32 oracle mode on GPU: torch composition
+        # MAML355_FCONV=0 (or another dtype): torch composition
         return ref.task_linear(x, w.to(x.dtype), b.to(x.dtype) if b is not None else None)
     return _LinFwdFn.apply(x.contiguous(), w, b)
 

@@ -7,6 +7,8 @@
     python tools/bench_kernels.py --ln-model        # ... plus whole-model A/B
     python tools/bench_kernels.py --wgrad           # wgrad v1 / v2 / v3 per shape
     python tools/bench_kernels.py --conv-input      # pad copy / first-layer fwd A/B
+    python tools/bench_kernels.py --fconv           # fp32 conv trio vs grouped ATen
+    python tools/bench_kernels.py --fconv-model     # fp32 modes, whole-model A/B
 
 Prints per-kernel time, effective TFLOP/s (conv) or TB/s (memory-bound),
 so optimization effort goes where the roofline says.
@@ -567,9 +569,163 @@ def main_strided(with_model):
         bench_strided_model("maml++_omniglot_20w5s", 128)
 
 
+FP32_MATRIX_PEAK = 157.3e12   # v_mfma_f32_16x16x4_f32, spec
+
+
+def bench_fconv(T, NB, H, W, C, F, tag, pad=1):
+    """fp32 stride-1 conv trio (fconv.hip, through the entry points the
+    autograd Functions use, repack included) against the grouped-ATen
+    forward ``ref.task_conv3x3`` and its autograd backward on the same fp32
+    tensors.  Per call: ms, TF, the fraction of the fp32 matrix peak and the
+    fraction of the byte floor (every operand and the result once over HBM)."""
+    from howtotrainyourmamlpytorch_amd.ops import reference as ref
+    dev = torch.device("cuda")
+    ext = hip_ext()
+    x = torch.randn(T, NB, H, W, C, device=dev)
+    w = torch.randn(T, F, C, 3, 3, device=dev).mul(0.1)
+    b = torch.randn(T, F, device=dev)
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    dy = torch.randn(T, NB, Ho, Wo, F, device=dev)
+    flops = 2.0 * T * NB * Ho * Wo * F * 9 * C
+    nbytes = 4.0 * (x.numel() + dy.numel() + w.numel())
+    first = C < 8   # first layer: no dgrad in the net (x is the image)
+
+    def k_fwd():
+        ext.fconv_mm(x, ext.fconv_repack(w, False), b, pad, Ho, Wo)
+
+    def k_dgrad():
+        ext.fconv_mm(dy, ext.fconv_repack(w, True), None, 2 - pad, H, W)
+
+    def k_wgrad():
+        ext.fconv_wgrad(dy, x, pad, True)
+
+    xr = x.clone().requires_grad_(True)
+    wr = w.clone().requires_grad_(True)
+    br = b.clone().requires_grad_(True)
+    yr = ref.task_conv3x3(xr, wr, br, 1, pad)
+
+    def r_fwd():
+        with torch.no_grad():
+            ref.task_conv3x3(x, w, b, 1, pad)
+
+    def r_dgrad():
+        torch.autograd.grad(yr, xr, dy, retain_graph=True)
+
+    def r_wgrad():
+        torch.autograd.grad(yr, (wr, br), dy, retain_graph=True)
+
+    def col(name, k, r):
+        return (f"{name} kernel {k*1e3:7.3f}ms {flops/k/1e12:5.1f}TF "
+                f"{100*flops/k/FP32_MATRIX_PEAK:4.1f}%peak "
+                f"{100*nbytes/HBM_BPS/k:4.1f}%bytefloor | "
+                f"ATen {r*1e3:8.3f}ms x{r/k:5.1f}")
+
+    kf, rf = _median_rounds([k_fwd, r_fwd], rounds=3, reps=5, warmup=2)
+    kw, rw = _median_rounds([k_wgrad, r_wgrad], rounds=3, reps=5, warmup=2)
+    line = f"[fconv {tag}] T{T} NB{NB} {H}x{W} C{C}->F{F} | " + col("fwd", kf, rf)
+    if first:
+        line += " | dgrad n/a (image input)"
+    else:
+        kd, rd = _median_rounds([k_dgrad, r_dgrad], rounds=3, reps=5, warmup=2)
+        line += " | " + col("dgrad", kd, rd)
+    line += " | " + col("wgrad", kw, rw)
+    print(line, flush=True)
+
+
+def bench_fconv_model(model_name, tasks_per_gpu, mode, steps=3, warmup=2,
+                      rounds=3):
+    """Whole-model second-order MSL step with fp32 activations on synthetic
+    episodes (bench.py's configuration plus ``mode``: "support" =
+    --fp32_support_pass True, "fp32" = --compute_dtype fp32): the fp32
+    kernels against MAML355_FCONV=0, alternating rounds in one process.
+    Prints every round, so the spread between rounds can be read off."""
+    import argparse
+    import os
+    import bench
+    from howtotrainyourmamlpytorch_amd.data import SyntheticEpisodeStream
+    from howtotrainyourmamlpytorch_amd.meta.engine import MAMLFewShotClassifier
+
+    cli = argparse.Namespace(model=model_name, tasks_per_gpu=tasks_per_gpu,
+                             inner_steps=5, second_order="True")
+    args = bench.build_args(cli, 1)
+    if mode == "support":
+        args.fp32_support_pass = True
+    else:
+        args.compute_dtype = "fp32"
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = MAMLFewShotClassifier(
+        im_shape=(2, args.image_channels, args.image_height, args.image_width),
+        device=dev, args=args)
+    stream = SyntheticEpisodeStream(args)
+    batches = [tuple(t.to(dev) for t in b) for b in stream.get_train_batches(4)]
+    saved = os.environ.get("MAML355_FCONV")
+
+    def run(old):
+        import warnings
+        os.environ["MAML355_FCONV"] = "0" if old else "1"
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")   # the A/B side warns
+                for i in range(warmup):
+                    model.run_train_iter(batches[i % 4], epoch=0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(steps):
+                    model.run_train_iter(batches[i % 4], epoch=0)
+                torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps
+        finally:
+            if saved is None:
+                os.environ.pop("MAML355_FCONV", None)
+            else:
+                os.environ["MAML355_FCONV"] = saved
+
+    tk, to = [], []
+    try:
+        for _ in range(rounds):
+            tk.append(run(False))
+            to.append(run(True))
+    except torch.cuda.OutOfMemoryError:
+        print(f"[fconv model {model_name} {mode}] {tasks_per_gpu} tasks/step: "
+              f"out of memory (kernel runs so far: {tk})", flush=True)
+        return
+    mk, mo = sorted(tk)[len(tk) // 2], sorted(to)[len(to) // 2]
+    rk = " ".join(f"{1/t:.3f}" for t in tk)
+    ro = " ".join(f"{1/t:.3f}" for t in to)
+    spread = max(max(tk) - min(tk), max(to) - min(to))
+    print(f"[fconv model {model_name} {mode}] {tasks_per_gpu} tasks/step, 2nd "
+          f"order MSL | kernels {1/mk:.3f} steps/s (rounds {rk}) | "
+          f"MAML355_FCONV=0 {1/mo:.3f} steps/s (rounds {ro}) | x{mo/mk:.2f}; "
+          f"difference {abs(mo-mk)*1e3:.1f} ms/step vs 3x round spread "
+          f"{3*spread*1e3:.1f} ms/step", flush=True)
+
+
+def main_fconv(with_model):
+    if "--fconv" in sys.argv:
+        # support-pass shapes: mini-imagenet 5w1s at 128 tasks (5 images)
+        bench_fconv(128, 5, 84, 84, 3, 48, "mi-s0-sup")
+        bench_fconv(128, 5, 42, 42, 48, 48, "mi-s1-sup")
+        bench_fconv(128, 5, 21, 21, 48, 48, "mi-s2-sup")
+        bench_fconv(128, 5, 10, 10, 48, 48, "mi-s3-sup")
+        # omniglot 20w5s at 32 tasks (100 images)
+        bench_fconv(32, 100, 28, 28, 1, 64, "om-s0-sup")
+        bench_fconv(32, 100, 14, 14, 64, 64, "om-s1-sup")
+        bench_fconv(32, 100, 7, 7, 64, 64, "om-s2-sup")
+        bench_fconv(32, 100, 3, 3, 64, 64, "om-s3-sup")
+    if with_model:
+        # the task counts of the per-call shapes above: 128 and 32 per step
+        for mode in ("support", "fp32"):
+            bench_fconv_model("maml++_miniimagenet_5w1s", 128, mode)
+            bench_fconv_model("maml++_omniglot_20w5s", 32, mode)
+
+
 def main():
     assert torch.cuda.is_available()
     print(torch.cuda.get_device_name(0))
+    if "--fconv" in sys.argv or "--fconv-model" in sys.argv:
+        main_fconv("--fconv-model" in sys.argv)
+        return
     if "--ln" in sys.argv or "--ln-model" in sys.argv:
         main_ln()
         return
