@@ -671,11 +671,6 @@ namespace {
 constexpr int kRowsPerBlock = 256;
 constexpr int kThreads = 256;
 
-int norm_grid(long total) {
-  long blocks = (total + kThreads - 1) / kThreads;
-  return (int)std::min<long>(blocks, 4096);
-}
-
 template <typename scalar_t>
 void bn_fwd_impl(const torch::Tensor& x, const torch::Tensor& gamma,
                  const torch::Tensor& beta, torch::Tensor& y,
@@ -726,7 +721,7 @@ void bn_fwd_impl(const torch::Tensor& x, const torch::Tensor& gamma,
                          T, M, C, (float)slope, kRowsPerBlock);                \
     } else {                                                                   \
       hipLaunchKernelGGL((bn_norm_act_kernel<scalar_t, PT, ACT_>),             \
-                         dim3(norm_grid(total)), dim3(kThreads), 0,            \
+                         dim3(ew_grid(total, kThreads)), dim3(kThreads), 0,    \
                          stream.stream(),                                      \
                          reinterpret_cast<const scalar_t*>(x.data_ptr()),      \
                          reinterpret_cast<scalar_t*>(y.data_ptr()),            \
@@ -794,7 +789,7 @@ void bn_bwd_impl(const torch::Tensor& dy, const torch::Tensor& x,
                        bsums.data_ptr<float>(), T, M, C, (float)slope,         \
                        kRowsPerBlock);                                         \
     hipLaunchKernelGGL((bn_bwd_dx_kernel<scalar_t, PT, ACT_>),                 \
-                       dim3(norm_grid(total)), dim3(kThreads), 0,              \
+                       dim3(ew_grid(total, kThreads)), dim3(kThreads), 0,      \
                        stream.stream(),                                        \
                        reinterpret_cast<const scalar_t*>(dy.data_ptr()),       \
                        reinterpret_cast<const scalar_t*>(x.data_ptr()),        \

@@ -173,10 +173,6 @@ __global__ void bn_dbwd_apply_kernel(const scalar_t* __restrict__ x,
 namespace {
 constexpr int kRowsPerBlockD = 256;
 constexpr int kThreadsD = 256;
-int grid_ew(long total) {
-  long b = (total + kThreadsD - 1) / kThreadsD;
-  return (int)std::min<long>(b, 4096);
-}
 }  // namespace
 
 // returns {d_u, d_x, sums[T,5,C]} — d_gamma_t is finished by the wrapper:
@@ -226,8 +222,9 @@ std::vector<torch::Tensor> bn_act_dbwd(torch::Tensor x, torch::Tensor u,
                        dim3(256), 0, stream.stream(),                          \
                        partials.data_ptr<float>(), sums.data_ptr<float>(),     \
                        T, nblk, C);                                            \
-    hipLaunchKernelGGL((bn_dbwd_apply_kernel<ST, PT>), dim3(grid_ew(total)),   \
-                       dim3(kThreadsD), 0, stream.stream(),                    \
+    hipLaunchKernelGGL((bn_dbwd_apply_kernel<ST, PT>),                         \
+                       dim3(ew_grid(total, kThreadsD)), dim3(kThreadsD), 0,    \
+                       stream.stream(),                                        \
                        reinterpret_cast<const ST*>(x.data_ptr()),              \
                        reinterpret_cast<const ST*>(uc.data_ptr()),             \
                        reinterpret_cast<const ST*>(gxc.data_ptr()),            \

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <algorithm>
+
 #define WAVE 64
 #define DEVINL __device__ __forceinline__
 
@@ -42,6 +44,13 @@ DEVINL float block_reduce_sum(float v, float* lds) {
 
 // grid-stride loop bound: cap resident blocks, stride the rest (guide G11)
 DEVINL long grid_stride() { return (long)blockDim.x * gridDim.x; }
+
+// host side of the same: blocks for an element-wise kernel over `total`
+// items, at least one, at most 4096 (the kernel strides over the rest)
+inline int ew_grid(long total, int threads = 256) {
+  const long blocks = (total + threads - 1) / threads;
+  return (int)std::min<long>(std::max<long>(blocks, 1), 4096);
+}
 
 template <typename T>
 DEVINL float to_f32(T v);

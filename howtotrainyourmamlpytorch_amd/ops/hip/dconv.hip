@@ -18,6 +18,7 @@
 // Both are FMA-throughput bound by construction instead of staging bound.
 
 #include "common.h"
+#include "conv_host.h"
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -337,28 +338,6 @@ void dconv_wgrad_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ X,
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-// local copy of the slice-summing finalize (same as tconv.hip's — kept
-// per-TU because the build is non-RDC)
-__global__ void dconv_finalize_kernel(const float* __restrict__ acc,
-                                      float* __restrict__ dw,
-                                      int T, int F, int C, int nslices) {
-  const long total = (long)T * F * C * 9;
-  const long ssz = (long)9 * C * F;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += grid_stride()) {
-    long r = i;
-    const int kx = (int)(r % 3); r /= 3;
-    const int ky = (int)(r % 3); r /= 3;
-    const int c = (int)(r % C); r /= C;
-    const int f = (int)(r % F); r /= F;
-    const long t = r;
-    const long e = ((long)(ky * 3 + kx) * C + c) * F + f;
-    float v = 0.f;
-    for (int s = 0; s < nslices; ++s) v += acc[(t * nslices + s) * ssz + e];
-    dw[i] = v;
-  }
-}
-
 torch::Tensor dconv_fwd(torch::Tensor x, torch::Tensor w,
                         c10::optional<torch::Tensor> bias, long pad,
                         long Ho, long Wo) {
@@ -441,8 +420,7 @@ std::vector<torch::Tensor> dconv_wgrad(torch::Tensor dy, torch::Tensor x,
             W = (int)x.size(3), C = (int)x.size(4);
   const int Ho = (int)dy.size(2), Wo = (int)dy.size(3), F = (int)dy.size(4);
   TORCH_CHECK(C <= 8 && F <= 64, "dconv_wgrad needs C<=8, F<=64");
-  const char* det_env = getenv("MAML355_DETERMINISTIC");
-  const bool det = det_env && det_env[0] == '1';
+  const bool det = deterministic_mode();
   const long Mtot = (long)NB * Ho * Wo;
   // chunk so total waves fill the chip (4 waves per block)
   long gridx = std::max<long>(1, 2048 / std::max(1, T));
@@ -474,12 +452,5 @@ std::vector<torch::Tensor> dconv_wgrad(torch::Tensor dy, torch::Tensor x,
   }
 #undef LAUNCH_DWG
 #undef LAUNCH_DWG_DET
-  auto dw = torch::empty({T, F, C, 3, 3}, x.options().dtype(torch::kFloat32));
-  const long total = (long)T * F * C * 9;
-  const int fb = (int)std::min<long>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(dconv_finalize_kernel, dim3(fb), dim3(256), 0,
-                     stream.stream(), acc.data_ptr<float>(),
-                     dw.data_ptr<float>(), T, F, C, nslices);
-  auto db = nslices == 1 ? dbacc.select(1, 0).contiguous() : dbacc.sum(1);
-  return {dw, db};
+  return finish_wgrad(acc, dbacc, T, F, C, nslices, stream.stream());
 }

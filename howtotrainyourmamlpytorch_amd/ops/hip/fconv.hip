@@ -26,21 +26,13 @@
 // all three ops are bitwise run-to-run reproducible in every mode.
 
 #include "common.h"
+#include "wgrad_plan.h"
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
 using namespace maml355;
 
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
-
-namespace {
-
-static int fc_grid(long total, int threads) {
-  long b = (total + threads - 1) / threads;
-  return (int)std::min<long>(std::max<long>(b, 1), 4096);
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------------------
 // Weight repack: W [T, F, C, 3, 3] fp32 -> Wp [T, 9, Ci, Co] fp32 (a pure
@@ -279,6 +271,8 @@ void fconv_mm_kernel(const float* __restrict__ X, const float* __restrict__ Wp,
 // ---------------------------------------------------------------------------
 #define WFN 64
 #define WFK 32
+static_assert(WFK == wgplan::kStepF32 && WFN == wgplan::kCols,
+              "wgrad_plan.h cuts K-chunks for these tiles");
 #define WLD 80
 
 template <int MT>   // 16-row tiles of F: ceil(F / 16), compile-time (as NT)
@@ -504,7 +498,7 @@ torch::Tensor fconv_repack(torch::Tensor w, bool dgrad) {
   auto stream = at::cuda::getCurrentCUDAStream();
   const long total = (long)T * F * C * 9;
   if (total == 0) return wp;
-  hipLaunchKernelGGL(fconv_repack_kernel, dim3(fc_grid(total, 256)), dim3(256),
+  hipLaunchKernelGGL(fconv_repack_kernel, dim3(ew_grid(total)), dim3(256),
                      0, stream.stream(), wc.data_ptr<float>(),
                      wp.data_ptr<float>(), T, F, C, dgrad);
   return wp;
@@ -581,24 +575,21 @@ std::vector<torch::Tensor> fconv_wgrad(torch::Tensor dy, torch::Tensor x,
   auto dw = torch::empty({T, F, C, 3, 3}, fopts);
   auto db = torch::zeros({T, F}, fopts);
   if (T == 0 || Ktot == 0) return {dw.zero_(), db};
-  // size K-chunks so the grid has ~3072 blocks: small support-pass
+  // K-chunks sized so the grid has ~3072 blocks: small support-pass
   // reductions would otherwise leave most of the chip idle, and a grid of
   // a few blocks per CU ends on a long partial round
-  const int gridx = (N9 + WFN - 1) / WFN;
-  long desired_y = std::max<long>(1, 3072 / std::max<long>(1, (long)gridx * T));
-  long kchunk = (Ktot + desired_y - 1) / desired_y;
-  kchunk = std::max<long>(((kchunk + WFK - 1) / WFK) * WFK, WFK);
-  const int nsl = (int)((Ktot + kchunk - 1) / kchunk);
+  const wgplan::Plan p = wgplan::fconv(T, NB, Ho, Wo, C);
+  const int nsl = p.nslices;
   auto sl = torch::empty({T, nsl, N9, F}, fopts);
   auto dbsl = torch::empty({T, nsl, F}, fopts);
-  dim3 grid((unsigned)gridx, (unsigned)nsl, T);
+  dim3 grid((unsigned)p.gridx, (unsigned)nsl, T);
   auto stream = at::cuda::getCurrentCUDAStream();
 #define LAUNCH_FWG(MT_)                                                        \
   hipLaunchKernelGGL((fconv_wgrad_kernel<MT_>), grid, dim3(256), 0,            \
                      stream.stream(), dyc.data_ptr<float>(),                   \
                      xc.data_ptr<float>(), sl.data_ptr<float>(),               \
                      with_bias ? dbsl.data_ptr<float>() : nullptr, T, NB, H,   \
-                     W, C, Ho, Wo, F, (int)pad, (int)kchunk)
+                     W, C, Ho, Wo, F, (int)pad, p.kchunk)
   switch ((F + 15) / 16) {
     case 1: LAUNCH_FWG(1); break;
     case 2: LAUNCH_FWG(2); break;
@@ -607,7 +598,7 @@ std::vector<torch::Tensor> fconv_wgrad(torch::Tensor dy, torch::Tensor x,
   }
 #undef LAUNCH_FWG
   const long total = (long)T * F * C * 9;
-  hipLaunchKernelGGL(fconv_wgrad_finalize_kernel, dim3(fc_grid(total, 256)),
+  hipLaunchKernelGGL(fconv_wgrad_finalize_kernel, dim3(ew_grid(total)),
                      dim3(256), 0, stream.stream(), sl.data_ptr<float>(),
                      with_bias ? dbsl.data_ptr<float>() : nullptr,
                      dw.data_ptr<float>(), db.data_ptr<float>(), T, F, C, nsl);

@@ -104,11 +104,6 @@ __global__ void gavgpool_bwd_kernel(const bf16* __restrict__ dy,
   }
 }
 
-static int gap_grid(long total, int threads) {
-  long blocks = (total + threads - 1) / threads;
-  return (int)std::min<long>(std::max<long>(blocks, 1), 4096);
-}
-
 // x [N, H, W, C] bf16 contiguous (caller flattens T*NS -> N) -> y [N, C]
 torch::Tensor gavgpool_fwd(torch::Tensor x) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
@@ -120,12 +115,12 @@ torch::Tensor gavgpool_fwd(torch::Tensor x) {
   auto stream = at::cuda::getCurrentCUDAStream();
   if (C % 8 == 0) {
     hipLaunchKernelGGL(gavgpool_fwd_vec_kernel,
-                       dim3(gap_grid(N * (C / 8) * GAP_SPLIT, 256)), dim3(256), 0,
+                       dim3(ew_grid(N * (C / 8) * GAP_SPLIT, 256)), dim3(256), 0,
                        stream.stream(),
                        reinterpret_cast<const bf16*>(x.data_ptr()),
                        reinterpret_cast<bf16*>(y.data_ptr()), N, HW, C);
   } else {
-    hipLaunchKernelGGL(gavgpool_fwd_kernel, dim3(gap_grid(N * C, 256)),
+    hipLaunchKernelGGL(gavgpool_fwd_kernel, dim3(ew_grid(N * C, 256)),
                        dim3(256), 0, stream.stream(),
                        reinterpret_cast<const bf16*>(x.data_ptr()),
                        reinterpret_cast<bf16*>(y.data_ptr()), N, HW, C);
@@ -144,12 +139,12 @@ torch::Tensor gavgpool_bwd(torch::Tensor dy, long H, long W) {
   auto stream = at::cuda::getCurrentCUDAStream();
   if (C % 8 == 0) {
     hipLaunchKernelGGL(gavgpool_bwd_vec_kernel,
-                       dim3(gap_grid(N * HW * (C / 8), 256)), dim3(256), 0,
+                       dim3(ew_grid(N * HW * (C / 8), 256)), dim3(256), 0,
                        stream.stream(),
                        reinterpret_cast<const bf16*>(dyc.data_ptr()),
                        reinterpret_cast<bf16*>(dx.data_ptr()), N, HW, C);
   } else {
-    hipLaunchKernelGGL(gavgpool_bwd_kernel, dim3(gap_grid(N * HW * C, 256)),
+    hipLaunchKernelGGL(gavgpool_bwd_kernel, dim3(ew_grid(N * HW * C, 256)),
                        dim3(256), 0, stream.stream(),
                        reinterpret_cast<const bf16*>(dyc.data_ptr()),
                        reinterpret_cast<bf16*>(dx.data_ptr()), N, HW, C);

@@ -144,11 +144,6 @@ __global__ void lin_db_kernel(const AT* __restrict__ dY,
   dB[i] = acc;
 }
 
-static int lgrid(long total, int threads) {
-  long b = (total + threads - 1) / threads;
-  return (int)std::min<long>(b, 4096);
-}
-
 static bool lin_is_f32(const torch::Tensor& a, const char* what) {
   TORCH_CHECK(a.scalar_type() == torch::kBFloat16 ||
                   a.scalar_type() == torch::kFloat32,
@@ -173,7 +168,7 @@ torch::Tensor lin_fwd(torch::Tensor x, torch::Tensor w,
     bptr = bc.data_ptr<float>();
   }
   auto stream = at::cuda::getCurrentCUDAStream();
-  const dim3 grid(lgrid((long)T * M * WAVE, 256));
+  const dim3 grid(ew_grid((long)T * M * WAVE, 256));
   if (f32) {
     hipLaunchKernelGGL(lin_fwd_kernel<float>, grid, dim3(256), 0,
                        stream.stream(), xc.data_ptr<float>(),
@@ -198,7 +193,7 @@ torch::Tensor lin_dx(torch::Tensor dy, torch::Tensor w) {
   const int K = (int)w.size(2);
   auto dx = torch::empty({T, M, K}, dy.options());
   auto stream = at::cuda::getCurrentCUDAStream();
-  const dim3 grid(lgrid((long)T * M * K, 256));
+  const dim3 grid(ew_grid((long)T * M * K, 256));
   if (f32) {
     hipLaunchKernelGGL(lin_dx_kernel<float>, grid, dim3(256), 0,
                        stream.stream(), dyc.data_ptr<float>(),
@@ -227,7 +222,7 @@ std::vector<torch::Tensor> lin_wgrad(torch::Tensor dy, torch::Tensor x,
   auto dw = torch::empty({T, ways, K}, x.options().dtype(torch::kFloat32));
   auto db = torch::empty({T, ways}, x.options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentCUDAStream();
-  const dim3 grid(lgrid((long)T * ways * K, 256));
+  const dim3 grid(ew_grid((long)T * ways * K, 256));
   const dim3 bgrid((T * ways + 255) / 256);
   if (f32) {
     hipLaunchKernelGGL(lin_wgrad_kernel<float>, grid, dim3(256), 0,

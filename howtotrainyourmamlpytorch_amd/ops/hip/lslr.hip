@@ -45,11 +45,6 @@ __global__ void lslr_bwd_kernel(const float* __restrict__ gout,
   }
 }
 
-static int grid_for(long total, int threads) {
-  long blocks = (total + threads - 1) / threads;
-  return (int)std::min<long>(blocks, 4096);
-}
-
 torch::Tensor lslr_fwd(torch::Tensor arena, torch::Tensor grad,
                        torch::Tensor lr_vec) {
   TORCH_CHECK(arena.is_cuda() && arena.dim() == 2 && arena.is_contiguous());
@@ -57,7 +52,7 @@ torch::Tensor lslr_fwd(torch::Tensor arena, torch::Tensor grad,
   const long P = arena.size(1);
   auto out = torch::empty_like(arena);
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(lslr_fwd_kernel, dim3(grid_for(T * P, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(lslr_fwd_kernel, dim3(ew_grid(T * P, 256)), dim3(256), 0,
                      stream.stream(), arena.data_ptr<float>(),
                      grad.contiguous().data_ptr<float>(),
                      lr_vec.contiguous().data_ptr<float>(),
@@ -74,7 +69,7 @@ std::vector<torch::Tensor> lslr_bwd(torch::Tensor gout, torch::Tensor grad,
   auto dgrad = torch::empty_like(goutc);
   auto dlr = torch::empty({P}, gout.options());
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(lslr_bwd_kernel, dim3(grid_for(P, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(lslr_bwd_kernel, dim3(ew_grid(P, 256)), dim3(256), 0,
                      stream.stream(), goutc.data_ptr<float>(),
                      gradc.data_ptr<float>(),
                      lr_vec.contiguous().data_ptr<float>(),

@@ -143,11 +143,6 @@ __global__ void maxpool_bwd_vec_kernel(const scalar_t* __restrict__ dy,
   }
 }
 
-static int ew_grid(long total, int threads) {
-  long blocks = (total + threads - 1) / threads;
-  return (int)std::min<long>(blocks, 4096);
-}
-
 // x: [N, H, W, C] contiguous (caller flattens T*NS -> N)
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor x) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());

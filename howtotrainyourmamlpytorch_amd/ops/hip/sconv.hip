@@ -24,6 +24,8 @@
 // barriers into XOR-swizzled LDS tiles, BM=256, 8 waves, BK=64.
 
 #include "common.h"
+#include "conv_host.h"
+#include "wgrad_plan.h"
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -44,7 +46,8 @@ DEVINL int sswz64(int row, int col) {
 #define SKMAX 576      // 9 * 64
 #define SWBK 64        // wgrad K-step
 #define SWGN 64        // wgrad output columns per block (4 waves x 16)
-#define SWG_KCHUNK 4096
+static_assert(SWBK == wgplan::kStep && SWGN == wgplan::kCols,
+              "wgrad_plan.h cuts K-chunks for these tiles");
 
 // ---------------------------------------------------------------------------
 // Weight repack: W [T, F, C, 3, 3] fp32 -> Wp [T, 9, Ci, Co] bf16
@@ -71,30 +74,6 @@ __global__ void sconv_repack_kernel(const float* __restrict__ w,
       o = (((t * 9 + (long)(ky * 3 + kx)) * F + f) * C) + c;
     }
     wp[o] = __float2bfloat16(w[i]);
-  }
-}
-
-// fp32 wgrad accumulator [T, nslices, 9C, F] -> dW [T, F, C, 3, 3] fp32;
-// slices summed in FIXED order (nslices=1 on the atomic fast path)
-__global__ void sconv_wgrad_finalize_kernel(const float* __restrict__ acc,
-                                            float* __restrict__ dw,
-                                            int T, int F, int C, int nslices) {
-  const long total = (long)T * F * C * 9;
-  const long ssz = (long)9 * C * F;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += grid_stride()) {
-    long r = i;
-    const int kx = (int)(r % 3); r /= 3;
-    const int ky = (int)(r % 3); r /= 3;
-    const int c = (int)(r % C); r /= C;
-    const int f = (int)(r % F); r /= F;
-    const long t = r;
-    const long e = ((long)(ky * 3 + kx) * C + c) * F + f;
-    float v = 0.f;
-    for (int s = 0; s < nslices; ++s) {
-      v += acc[(t * nslices + s) * ssz + e];
-    }
-    dw[i] = v;
   }
 }
 
@@ -501,10 +480,6 @@ void sconv_wgrad_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ X,
 // launchers
 // ---------------------------------------------------------------------------
 namespace {
-int sew_grid(long total, int threads) {
-  long blocks = (total + threads - 1) / threads;
-  return (int)std::min<long>(std::max<long>(blocks, 1), 4096);
-}
 long sconv_out_dim(long h, long pad) { return (h + 2 * pad - 3) / 2 + 1; }
 }  // namespace
 
@@ -517,7 +492,7 @@ torch::Tensor sconv_repack(torch::Tensor w, bool dgrad) {
                          w.options().dtype(torch::kBFloat16));
   auto stream = at::cuda::getCurrentCUDAStream();
   const long total = (long)T * F * C * 9;
-  hipLaunchKernelGGL(sconv_repack_kernel, dim3(sew_grid(total, 256)), dim3(256),
+  hipLaunchKernelGGL(sconv_repack_kernel, dim3(ew_grid(total)), dim3(256),
                      0, stream.stream(), wc.data_ptr<float>(),
                      reinterpret_cast<bf16*>(wp.data_ptr()), T, F, C, dgrad);
   return wp;
@@ -607,26 +582,16 @@ std::vector<torch::Tensor> sconv_wgrad(torch::Tensor dy, torch::Tensor x,
   TORCH_CHECK(H + 2 * pad >= 3 && W + 2 * pad >= 3 &&
               sconv_out_dim(H, pad) == Ho && sconv_out_dim(W, pad) == Wo,
               "sconv_wgrad: dy inconsistent with x");
-  const int N9 = 9 * C;
-  const long Ktot = (long)NB * Ho * Wo;
-  const char* det_env = getenv("MAML355_DETERMINISTIC");
-  const bool det = det_env && det_env[0] == '1';
-  // size K-chunks so the grid has >= ~1024 blocks, as tconv_wgrad does
-  const int gridx = (N9 + SWGN - 1) / SWGN;
-  long desired_y = std::max<long>(1, 1024 / std::max<long>(1, (long)gridx * T));
-  long kchunk = (Ktot + desired_y - 1) / desired_y;
-  kchunk = ((kchunk + SWBK - 1) / SWBK) * SWBK;
-  kchunk = std::max<long>(kchunk, SWBK);
-  if (!det) kchunk = std::min<long>(kchunk, SWG_KCHUNK);
-  const int gridy = (int)((Ktot + kchunk - 1) / kchunk);
+  const bool det = deterministic_mode();
+  // K-chunks sized so the grid has >= ~1024 blocks, as tconv_wgrad's.
   // MAML355_DETERMINISTIC: private per-(t, K-chunk) slices, summed in fixed
   // order by the finalize kernel -> bitwise reproducible
-  const int nslices = det ? gridy : 1;
-  auto acc = torch::zeros({T, nslices, N9, F},
+  const wgplan::Plan p = wgplan::sconv(T, NB, Ho, Wo, C, det);
+  auto acc = torch::zeros({T, p.nslices, 9 * C, F},
                           x.options().dtype(torch::kFloat32));
-  auto dbacc = torch::zeros({T, nslices, F},
+  auto dbacc = torch::zeros({T, p.nslices, F},
                             x.options().dtype(torch::kFloat32));
-  dim3 grid((unsigned)gridx, (unsigned)gridy, T);
+  dim3 grid((unsigned)p.gridx, (unsigned)p.gridy, T);
   auto stream = at::cuda::getCurrentCUDAStream();
 #define LAUNCH_SWGRAD(DET_)                                                    \
   hipLaunchKernelGGL((sconv_wgrad_kernel<DET_>), grid, dim3(256), 0,           \
@@ -635,14 +600,8 @@ std::vector<torch::Tensor> sconv_wgrad(torch::Tensor dy, torch::Tensor x,
                      reinterpret_cast<const bf16*>(xc.data_ptr()),             \
                      acc.data_ptr<float>(),                                    \
                      with_bias ? dbacc.data_ptr<float>() : nullptr,            \
-                     NB, H, W, C, Ho, Wo, F, (int)pad, (int)kchunk)
+                     NB, H, W, C, Ho, Wo, F, (int)pad, p.kchunk)
   if (det) LAUNCH_SWGRAD(true); else LAUNCH_SWGRAD(false);
 #undef LAUNCH_SWGRAD
-  auto dw = torch::empty({T, F, C, 3, 3}, x.options().dtype(torch::kFloat32));
-  const long total = (long)T * F * C * 9;
-  hipLaunchKernelGGL(sconv_wgrad_finalize_kernel, dim3(sew_grid(total, 256)),
-                     dim3(256), 0, stream.stream(), acc.data_ptr<float>(),
-                     dw.data_ptr<float>(), T, F, C, nslices);
-  auto db = nslices == 1 ? dbacc.select(1, 0).contiguous() : dbacc.sum(1);
-  return {dw, db};
+  return finish_wgrad(acc, dbacc, T, F, C, p.nslices, stream.stream());
 }

@@ -95,11 +95,6 @@ __global__ void ce_dbwd_kernel(const float* __restrict__ probs,
   }
 }
 
-static int grid_for(long total, int threads) {
-  long blocks = (total + threads - 1) / threads;
-  return (int)std::min<long>(blocks, 4096);
-}
-
 std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor labels) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 3);
   TORCH_CHECK(logits.size(2) <= WAVE, "ways must be <= 64");
@@ -112,7 +107,7 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor labels) {
   auto rowloss = torch::empty({T, M}, lf.options());
   auto stream = at::cuda::getCurrentCUDAStream();
   const long rows = (long)T * M;
-  hipLaunchKernelGGL(ce_fwd_kernel, dim3(grid_for(rows * WAVE, 256)), dim3(256),
+  hipLaunchKernelGGL(ce_fwd_kernel, dim3(ew_grid(rows * WAVE, 256)), dim3(256),
                      0, stream.stream(), lf.data_ptr<float>(),
                      lab.data_ptr<long>(), probs.data_ptr<float>(),
                      rowloss.data_ptr<float>(), T, M, ways);
@@ -134,7 +129,7 @@ std::vector<torch::Tensor> ce_dbwd(torch::Tensor probs, torch::Tensor labels,
   auto gtc = gtask.contiguous().to(torch::kFloat32);
   auto stream = at::cuda::getCurrentCUDAStream();
   const long rows = (long)T * M;
-  hipLaunchKernelGGL(ce_dbwd_kernel, dim3(grid_for(rows * WAVE, 256)),
+  hipLaunchKernelGGL(ce_dbwd_kernel, dim3(ew_grid(rows * WAVE, 256)),
                      dim3(256), 0, stream.stream(), probs.data_ptr<float>(),
                      lab.data_ptr<long>(), gdlc.data_ptr<float>(),
                      gtc.data_ptr<float>(), d_logits.data_ptr<float>(),
@@ -154,7 +149,7 @@ torch::Tensor ce_bwd(torch::Tensor probs, torch::Tensor labels,
   auto lab = labels.contiguous().to(torch::kLong);
   auto stream = at::cuda::getCurrentCUDAStream();
   const long total = (long)T * M * ways;
-  hipLaunchKernelGGL(ce_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(ce_bwd_kernel, dim3(ew_grid(total, 256)), dim3(256), 0,
                      stream.stream(), probs.data_ptr<float>(),
                      lab.data_ptr<long>(), gt.data_ptr<float>(),
                      dlogits.data_ptr<float>(), T, M, ways);

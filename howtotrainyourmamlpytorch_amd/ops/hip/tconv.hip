@@ -32,7 +32,9 @@
 // via LDS-occupancy / issue-pressure cliffs; r2: the pipeline ladder).
 
 #include "common.h"
+#include "conv_host.h"
 #include "tconv_mm_addr.h"
+#include "wgrad_plan.h"
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -119,10 +121,11 @@ __global__ void wgrad_finalize_kernel(const float* __restrict__ acc,
 // ---------------------------------------------------------------------------
 #define BM 256
 #define BK 64    // K-step: 2 MFMA K-slices per barrier
-#define WG_KCHUNK 4096
 #define WBK 64   // wgrad K-step (2 MFMA K-slices per barrier)
 
 #define WGN 64   // wgrad output columns per block (4 waves x 16)
+static_assert(WBK == wgplan::kStep && WGN == wgplan::kCols,
+              "wgrad_plan.h cuts K-chunks for these tiles");
 
 __global__ __launch_bounds__(512, 2)
 void tconv_mm_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wp,
@@ -1098,15 +1101,8 @@ __global__ void mfma_probe_kernel(const bf16* __restrict__ A,
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-namespace {
-int ew_grid2(long total, int threads) {
-  long blocks = (total + threads - 1) / threads;
-  return (int)std::min<long>(blocks, 4096);
-}
-
-// 16-byte-aligned zeros that tail and border lanes of the async staging read
-// instead of predicating: one page per device, allocated and filled once (a
-// torch::zeros per call is a fill-kernel launch per call).
+// conv_host.h: shared with wgrad_nt.hip, sconv.hip and dconv.hip
+namespace maml355 {
 const bf16* conv_zero_page(const torch::Tensor& like) {
   static auto* pages = new std::vector<torch::Tensor>(64);
   const int dev = like.get_device();
@@ -1115,7 +1111,19 @@ const bf16* conv_zero_page(const torch::Tensor& like) {
   if (!p.defined()) p = torch::zeros({128}, like.options());
   return reinterpret_cast<const bf16*>(p.data_ptr());
 }
-}  // namespace
+
+std::vector<torch::Tensor> finish_wgrad(const torch::Tensor& acc,
+                                        const torch::Tensor& dbacc, int T,
+                                        int F, int C, int nslices,
+                                        hipStream_t stream) {
+  auto dw = torch::empty({T, F, C, 3, 3}, acc.options());
+  hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(ew_grid((long)T * F * C * 9)),
+                     dim3(256), 0, stream, acc.data_ptr<float>(),
+                     dw.data_ptr<float>(), T, F, C, nslices);
+  auto db = nslices == 1 ? dbacc.select(1, 0).contiguous() : dbacc.sum(1);
+  return {dw, db};
+}
+}  // namespace maml355
 
 torch::Tensor tconv_repack(torch::Tensor w, bool dgrad) {
   TORCH_CHECK(w.is_cuda() && w.dim() == 5 && w.size(3) == 3 && w.size(4) == 3);
@@ -1125,7 +1133,7 @@ torch::Tensor tconv_repack(torch::Tensor w, bool dgrad) {
                          w.options().dtype(torch::kBFloat16));
   auto stream = at::cuda::getCurrentCUDAStream();
   const long total = (long)T * F * C * 9;
-  hipLaunchKernelGGL(repack_weight_kernel, dim3(ew_grid2(total, 256)), dim3(256),
+  hipLaunchKernelGGL(repack_weight_kernel, dim3(ew_grid(total, 256)), dim3(256),
                      0, stream.stream(), wc.data_ptr<float>(),
                      reinterpret_cast<bf16*>(wp.data_ptr()), T, F, C, dgrad);
   return wp;
@@ -1175,7 +1183,7 @@ torch::Tensor tconv_repack_v2(torch::Tensor w, bool dgrad) {
                           w.options().dtype(torch::kBFloat16));
   auto stream = at::cuda::getCurrentCUDAStream();
   const long total = (long)T * ksteps * 64 * BK;
-  hipLaunchKernelGGL(repack_v2_kernel, dim3(ew_grid2(total, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(repack_v2_kernel, dim3(ew_grid(total, 256)), dim3(256), 0,
                      stream.stream(), wc.data_ptr<float>(),
                      reinterpret_cast<bf16*>(out.data_ptr()), T, F, C, ksteps,
                      dgrad);
@@ -1214,7 +1222,7 @@ std::vector<torch::Tensor> tconv_mm_v2(torch::Tensor x, torch::Tensor wimg,
     Wp = W + 2 * (int)pad;
     xp = torch::empty({T, NB, Hp, Wp, Ci}, x.options());
     const long ptotal = (long)T * NB * Hp * Wp * (Ci / 8);
-    hipLaunchKernelGGL(pad_nhwc_kernel, dim3(ew_grid2(ptotal, 256)), dim3(256),
+    hipLaunchKernelGGL(pad_nhwc_kernel, dim3(ew_grid(ptotal, 256)), dim3(256),
                        0, stream.stream(),
                        reinterpret_cast<const bf16*>(x.data_ptr()),
                        reinterpret_cast<bf16*>(xp.data_ptr()),
@@ -1279,28 +1287,18 @@ std::vector<torch::Tensor> tconv_wgrad(torch::Tensor dy, torch::Tensor x,
             W = (int)x.size(3), C = (int)x.size(4);
   const int Ho = (int)dy.size(2), Wo = (int)dy.size(3), F = (int)dy.size(4);
   TORCH_CHECK(F <= 64, "F must be <= 64");
-  const int N9 = 9 * C;
-  const long Ktot = (long)NB * Ho * Wo;
-  const char* det_env = getenv("MAML355_DETERMINISTIC");
-  const bool det = det_env && det_env[0] == '1';
-  // size K-chunks so the grid has >= ~1024 blocks (256 CUs want far more
-  // workgroups than CUs; small support-pass K was leaving the chip idle)
-  const int gridx = (N9 + WGN - 1) / WGN;
-  long desired_y = std::max<long>(1, 1024 / std::max<long>(1, (long)gridx * T));
-  long kchunk = (Ktot + desired_y - 1) / desired_y;
-  kchunk = ((kchunk + WBK - 1) / WBK) * WBK;
-  kchunk = std::max<long>(kchunk, WBK);
-  if (!det) kchunk = std::min<long>(kchunk, WG_KCHUNK);
-  const int gridy = (int)((Ktot + kchunk - 1) / kchunk);
+  const bool det = deterministic_mode();
+  // K-chunks sized so the grid has >= ~1024 blocks (256 CUs want far more
+  // workgroups than CUs; small support-pass K was leaving the chip idle).
   // MAML355_DETERMINISTIC: each (t, K-chunk) block writes a private
   // accumulator slice (no fp32 atomics); slices are summed in fixed order
   // by the finalize kernel -> bitwise run-to-run reproducible wgrad.
-  const int nslices = det ? gridy : 1;
-  auto acc = torch::zeros({T, nslices, N9, F},
+  const wgplan::Plan p = wgplan::v1(T, NB, Ho, Wo, C, det);
+  auto acc = torch::zeros({T, p.nslices, 9 * C, F},
                           x.options().dtype(torch::kFloat32));
-  auto dbacc = torch::zeros({T, nslices, F},
+  auto dbacc = torch::zeros({T, p.nslices, F},
                             x.options().dtype(torch::kFloat32));
-  dim3 grid((unsigned)gridx, (unsigned)gridy, T);
+  dim3 grid((unsigned)p.gridx, (unsigned)p.gridy, T);
   auto stream = at::cuda::getCurrentCUDAStream();
 #define LAUNCH_WGRAD(DET_)                                                     \
   hipLaunchKernelGGL((tconv_wgrad_kernel<DET_>), grid, dim3(256), 0,           \
@@ -1309,16 +1307,10 @@ std::vector<torch::Tensor> tconv_wgrad(torch::Tensor dy, torch::Tensor x,
                      reinterpret_cast<const bf16*>(xc.data_ptr()),             \
                      acc.data_ptr<float>(),                                    \
                      with_bias ? dbacc.data_ptr<float>() : nullptr,            \
-                     T, NB, H, W, C, Ho, Wo, F, (int)pad, (int)kchunk)
+                     T, NB, H, W, C, Ho, Wo, F, (int)pad, p.kchunk)
   if (det) LAUNCH_WGRAD(true); else LAUNCH_WGRAD(false);
 #undef LAUNCH_WGRAD
-  auto dw = torch::empty({T, F, C, 3, 3}, x.options().dtype(torch::kFloat32));
-  const long total = (long)T * F * C * 9;
-  hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(ew_grid2(total, 256)),
-                     dim3(256), 0, stream.stream(), acc.data_ptr<float>(),
-                     dw.data_ptr<float>(), T, F, C, nslices);
-  auto db = nslices == 1 ? dbacc.select(1, 0).contiguous() : dbacc.sum(1);
-  return {dw, db};
+  return finish_wgrad(acc, dbacc, T, F, C, p.nslices, stream.stream());
 }
 
 // wgrad v2: transpose both operands into k-contiguous layouts, then the
@@ -1333,12 +1325,15 @@ std::vector<torch::Tensor> tconv_wgrad_v2(torch::Tensor dy, torch::Tensor x,
             W = (int)x.size(3), C = (int)x.size(4);
   const int Ho = (int)dy.size(2), Wo = (int)dy.size(3), F = (int)dy.size(4);
   TORCH_CHECK(F <= 64, "wgrad_v2 needs F <= 64");
-  const char* det_env = getenv("MAML355_DETERMINISTIC");
-  const bool det = det_env && det_env[0] == '1';
-  const int N9 = 9 * C;
-  const int Wo8 = ((Wo + 7) / 8) * 8;
+  const bool det = deterministic_mode();
+  // 128-column blocks (NSUB=2, 2x MFMA per barrier) pay only on large-K
+  // shapes (measured: conv1-tgt 94->104 TF; SLOWER below Kr ~1.3e5 — grid
+  // starvation + 48 KB LDS occupancy drop); the grid is sized as v1's
+  const wgplan::Plan p =
+      wgplan::v2(T, NB, Ho, Wo, C, det, wgrad_nsub_override());
+  const int Wo8 = p.Wk;
   const long Kprime = (long)NB * Ho * Wo8;
-  const long Kr = ((Kprime + WBK - 1) / WBK) * WBK;
+  const long Kr = p.Kr;
   const int Hxp = H + 2 * (int)pad;
   const int Wxp = Wo8 + 2;
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -1354,7 +1349,7 @@ std::vector<torch::Tensor> tconv_wgrad_v2(torch::Tensor dy, torch::Tensor x,
                        T, NB, Ho, Wo, F, Wo8, Kr);
     if (Kr > Kprime) {
       const long total = (long)T * F * (Kr - Kprime);
-      hipLaunchKernelGGL(dyt_tail_kernel, dim3(ew_grid2(total, 256)), dim3(256),
+      hipLaunchKernelGGL(dyt_tail_kernel, dim3(ew_grid(total, 256)), dim3(256),
                          0, stream.stream(),
                          reinterpret_cast<bf16*>(dyt.data_ptr()), T, F, Kprime,
                          Kr);
@@ -1370,31 +1365,11 @@ std::vector<torch::Tensor> tconv_wgrad_v2(torch::Tensor dy, torch::Tensor x,
                        T, NB, H, W, C, Hxp, Wxp, (int)pad);
   }
   const bf16* zpage = conv_zero_page(x);
-
-  // n-columns per block: NSUB=2 (128 cols, 2x MFMA per barrier) pays only
-  // on large-K shapes (measured: conv1-tgt 94->104 TF; SLOWER below
-  // Kr ~1.3e5 — grid starvation + 48 KB LDS occupancy drop).  Env
-  // MAML355_WGRAD_NSUB overrides for A/B.
-  int nsub = (N9 > 64 && Kr >= 131072) ? 2 : 1;
-  if (const char* e = getenv("MAML355_WGRAD_NSUB")) {
-    if (e[0] == '1') nsub = 1; else if (e[0] == '2' && N9 > 64) nsub = 2;
-  }
-  const int wgn = 64 * nsub;
-
-  // grid sizing as v1 (>= ~1024 blocks), K-chunks multiple of WBK
-  const int gridx = (N9 + wgn - 1) / wgn;
-  long desired_y = std::max<long>(1, 1024 / std::max<long>(1, (long)gridx * T));
-  long kchunk = (Kr + desired_y - 1) / desired_y;
-  kchunk = ((kchunk + WBK - 1) / WBK) * WBK;
-  kchunk = std::max<long>(kchunk, WBK);
-  if (!det) kchunk = std::min<long>(kchunk, (long)WG_KCHUNK);
-  const int gridy = (int)((Kr + kchunk - 1) / kchunk);
-  const int nslices = det ? gridy : 1;
-  auto acc = torch::zeros({T, nslices, N9, F},
+  auto acc = torch::zeros({T, p.nslices, 9 * C, F},
                           x.options().dtype(torch::kFloat32));
-  auto dbacc = torch::zeros({T, nslices, F},
+  auto dbacc = torch::zeros({T, p.nslices, F},
                             x.options().dtype(torch::kFloat32));
-  dim3 grid((unsigned)gridx, (unsigned)gridy, T);
+  dim3 grid((unsigned)p.gridx, (unsigned)p.gridy, T);
 #define LAUNCH_WG2(NS_, DET_)                                                  \
   hipLaunchKernelGGL((tconv_wgrad_v2_kernel<NS_, DET_>), grid, dim3(256), 0,   \
                      stream.stream(),                                          \
@@ -1402,28 +1377,14 @@ std::vector<torch::Tensor> tconv_wgrad_v2(torch::Tensor dy, torch::Tensor x,
                      reinterpret_cast<const bf16*>(xt.data_ptr()), zpage,      \
                      acc.data_ptr<float>(),                                    \
                      with_bias ? dbacc.data_ptr<float>() : nullptr,            \
-                     T, NB, Ho, Wo8, Hxp, Wxp, C, F, Kr, Kprime, (int)kchunk)
-  if (nsub == 2) {
+                     T, NB, Ho, Wo8, Hxp, Wxp, C, F, Kr, Kprime, p.kchunk)
+  if (p.nsub == 2) {
     if (det) LAUNCH_WG2(2, true); else LAUNCH_WG2(2, false);
   } else {
     if (det) LAUNCH_WG2(1, true); else LAUNCH_WG2(1, false);
   }
 #undef LAUNCH_WG2
-  auto dw = torch::empty({T, F, C, 3, 3}, x.options().dtype(torch::kFloat32));
-  const long total = (long)T * F * C * 9;
-  hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(ew_grid2(total, 256)),
-                     dim3(256), 0, stream.stream(), acc.data_ptr<float>(),
-                     dw.data_ptr<float>(), T, F, C, nslices);
-  auto db = nslices == 1 ? dbacc.select(1, 0).contiguous() : dbacc.sum(1);
-  return {dw, db};
-}
-
-// wgrad_finalize_kernel for callers in other translation units (wgrad_nt.hip)
-void launch_wgrad_finalize(const float* acc, float* dw, int T, int F, int C,
-                           int nslices, hipStream_t stream) {
-  const long total = (long)T * F * C * 9;
-  hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(ew_grid2(total, 256)),
-                     dim3(256), 0, stream, acc, dw, T, F, C, nslices);
+  return finish_wgrad(acc, dbacc, T, F, C, p.nslices, stream.stream());
 }
 
 std::vector<torch::Tensor> mfma_probe(torch::Tensor A, torch::Tensor B) {

@@ -25,7 +25,9 @@
 // LDS, as v2 does.
 
 #include "common.h"
+#include "conv_host.h"
 #include "wgrad_nt_addr.h"
+#include "wgrad_plan.h"
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -36,13 +38,14 @@ typedef __attribute__((__vector_size__(8 * sizeof(short)))) short bf16x8;
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
 typedef short bf16x4v __attribute__((ext_vector_type(4)));
 
-// tconv.hip
-void launch_wgrad_finalize(const float* acc, float* dw, int T, int F, int C,
-                           int nslices, hipStream_t stream);
+static_assert(wgnt::kRows == wgplan::kStep,
+              "wgrad_plan.h cuts K-chunks for this tile");
 
-#define NT_KCHUNK 4096
-
-enum { NT_BIAS_NONE = 0, NT_BIAS_ONES = 1, NT_BIAS_COLSUM = 2 };
+enum {
+  NT_BIAS_NONE = wgplan::kBiasNone,
+  NT_BIAS_ONES = wgplan::kBiasOnes,
+  NT_BIAS_COLSUM = wgplan::kBiasColsum
+};
 
 // x [M, C] (C < 8) -> xp [M, 8], zero-filled: the first layer's channel pad
 __global__ void nt_chpad8_kernel(const bf16* __restrict__ x,
@@ -251,17 +254,6 @@ void tconv_wgrad_nt_kernel(const bf16* __restrict__ dY,
   }
 }
 
-// constant zero page, one per device, allocated on first use and never
-// written afterwards
-static const bf16* nt_zero_page(const torch::Tensor& like) {
-  static auto* pages = new std::vector<torch::Tensor>(64);
-  const int dev = like.get_device();
-  TORCH_CHECK(dev >= 0 && dev < 64);
-  auto& p = (*pages)[dev];
-  if (!p.defined()) p = torch::zeros({128}, like.options());
-  return reinterpret_cast<const bf16*>(p.data_ptr());
-}
-
 // dy [T, NB, Ho, Wo, F] bf16 ; x [T, NB, H, W, C] bf16
 // -> {dw [T, F, C, 3, 3] fp32, db [T, F] fp32}; same contract as
 // tconv_wgrad_v2.  Needs F % 8 == 0, F <= 64 and C % 8 == 0 or C in {1, 3}.
@@ -282,8 +274,7 @@ std::vector<torch::Tensor> tconv_wgrad_v3(torch::Tensor dy, torch::Tensor x,
               Ho == H + 2 * pad - 2 && Wo == W + 2 * pad - 2 &&
               Ho >= 1 && Wo >= 1 && pad >= 0 && pad <= 2,
               "wgrad_v3: dy/x shapes do not match a 3x3 stride-1 conv");
-  const char* det_env = getenv("MAML355_DETERMINISTIC");
-  const bool det = det_env && det_env[0] == '1';
+  const bool det = deterministic_mode();
   auto stream = at::cuda::getCurrentCUDAStream();
 
   // first layer: pad the channels to one 16-byte chunk
@@ -292,7 +283,9 @@ std::vector<torch::Tensor> tconv_wgrad_v3(torch::Tensor dy, torch::Tensor x,
     Cp = 8;
     const long M = (long)T * NB * H * W;
     auto xp = torch::empty({T, NB, H, W, 8}, x.options());
-    hipLaunchKernelGGL(nt_chpad8_kernel, dim3((unsigned)std::min<long>((M + 255) / 256, 65536)), dim3(256), 0,
+    hipLaunchKernelGGL(nt_chpad8_kernel,
+                       dim3((unsigned)std::min<long>((M + 255) / 256, 65536)),
+                       dim3(256), 0,
                        stream.stream(),
                        reinterpret_cast<const bf16*>(xc.data_ptr()),
                        reinterpret_cast<bf16*>(xp.data_ptr()), M, C);
@@ -304,69 +297,34 @@ std::vector<torch::Tensor> tconv_wgrad_v3(torch::Tensor dy, torch::Tensor x,
   // 30 000 positions up, v1 below is flat —, the same K-chunks, the same
   // column-sum bias.  Zero rows add nothing, a column's accumulator does not
   // depend on its neighbours, and the k -> MFMA-lane map is theirs, so every
-  // fp32 operation is the one v2 / v1 performs.
-  const char* v2_env = getenv("MAML355_WGRAD_V2");
-  const bool as_v2 = det && (long)NB * Ho * Wo >= 30000 &&
-                     !(v2_env && v2_env[0] == '0');
-  const int Wk = as_v2 ? ((Wo + 7) / 8) * 8 : Wo;
-  const wgnt::Geom g = wgnt::make_geom(NB, H, W, Cp, Ho, Wo, F, (int)pad, Wk);
-  const long Kr = ((g.K + wgnt::kRows - 1) / wgnt::kRows) * wgnt::kRows;
-  const int N9 = g.N9;
-  const char* nsub_env = getenv("MAML355_WGRAD_NSUB");
-
+  // fp32 operation is the one v2 / v1 performs.  wgplan::v3 takes that
+  // plan's line width and K-chunks from wgplan::v2 / v1 themselves.
+  //
   // 128-column blocks stage dY half as often (once for the first layer's
   // 72 columns) but halve the grid and drop occupancy 4 -> 3 blocks/CU:
   // measured ahead (x1.06 - x1.46) from T * K of about 6e5 positions up,
   // behind (x0.57 - x0.90) below (profiles/README.md).  Env
   // MAML355_WGRAD_NSUB overrides for A/B.
-  int nsub = (N9 > 64 && (long)T * Kr >= 600000) ? 2 : 1;
-  if (nsub_env) {
-    if (nsub_env[0] == '1') nsub = 1;
-    else if (nsub_env[0] == '2' && N9 > 64) nsub = 2;
-  }
-  const int wgn = 64 * nsub;
-  const int gridx = (N9 + wgn - 1) / wgn;
-  int bias_mode = NT_BIAS_NONE;
-  if (with_bias)
-    bias_mode = (!det && gridx * wgn > N9) ? NT_BIAS_ONES : NT_BIAS_COLSUM;
-
-  // grid sizing as v2 (>= ~1024 blocks), K-chunks multiple of the tile.
-  // Deterministic: the chunks v2 / v1 would cut, i.e. sized by THEIR column
-  // grid over the unpadded 9C columns.
-  int gridx_k = gridx;
-  if (det) {
-    int nsub_old = 1;
-    if (as_v2) {
-      nsub_old = (9 * C > 64 && Kr >= 131072) ? 2 : 1;
-      if (nsub_env) {
-        if (nsub_env[0] == '1') nsub_old = 1;
-        else if (nsub_env[0] == '2' && 9 * C > 64) nsub_old = 2;
-      }
-    }
-    gridx_k = (9 * C + 64 * nsub_old - 1) / (64 * nsub_old);
-  }
-  const long klen = (det && !as_v2) ? g.K : Kr;   // v1 sizes by K, v2 by Kr
-  long desired_y = std::max<long>(1, 1024 / std::max<long>(1, (long)gridx_k * T));
-  long kchunk = (klen + desired_y - 1) / desired_y;
-  kchunk = ((kchunk + wgnt::kRows - 1) / wgnt::kRows) * wgnt::kRows;
-  kchunk = std::max<long>(kchunk, wgnt::kRows);
-  if (!det) kchunk = std::min<long>(kchunk, (long)NT_KCHUNK);
-  const int gridy = (int)((Kr + kchunk - 1) / kchunk);
-  TORCH_CHECK(gridy <= 65535 && T <= 65535, "wgrad_v3: grid too large");
-  const int nslices = det ? gridy : 1;
+  const char* v2_env = getenv("MAML355_WGRAD_V2");
+  const wgplan::Plan p =
+      wgplan::v3(T, NB, Ho, Wo, C, with_bias, det,
+                 !(v2_env && v2_env[0] == '0'), wgrad_nsub_override());
+  const wgnt::Geom g =
+      wgnt::make_geom(NB, H, W, Cp, Ho, Wo, F, (int)pad, p.Wk);
+  TORCH_CHECK(p.gridy <= 65535 && T <= 65535, "wgrad_v3: grid too large");
   auto fopt = x.options().dtype(torch::kFloat32);
-  auto acc = torch::zeros({T, nslices, 9 * C, F}, fopt);
-  auto dbacc = torch::zeros({T, nslices, F}, fopt);
-  const bf16* zpage = nt_zero_page(x);
-  dim3 grid((unsigned)gridx, (unsigned)gridy, T);
+  auto acc = torch::zeros({T, p.nslices, 9 * C, F}, fopt);
+  auto dbacc = torch::zeros({T, p.nslices, F}, fopt);
+  const bf16* zpage = conv_zero_page(x);
+  dim3 grid((unsigned)p.gridx, (unsigned)p.gridy, T);
 #define LAUNCH_NT(NS_, MT_, DET_)                                              \
   hipLaunchKernelGGL((tconv_wgrad_nt_kernel<NS_, MT_, DET_>), grid, dim3(256), \
                      0, stream.stream(),                                       \
                      reinterpret_cast<const bf16*>(dyc.data_ptr()),            \
                      reinterpret_cast<const bf16*>(xc.data_ptr()), zpage,      \
                      acc.data_ptr<float>(),                                    \
-                     with_bias ? dbacc.data_ptr<float>() : nullptr, g, C, Kr,  \
-                     (int)kchunk, bias_mode)
+                     with_bias ? dbacc.data_ptr<float>() : nullptr, g, C,      \
+                     p.Kr, p.kchunk, p.bias)
 #define LAUNCH_NT_MT(NS_, DET_)                                                \
   switch ((F + 15) / 16) {                                                     \
     case 1: LAUNCH_NT(NS_, 1, DET_); break;                                    \
@@ -374,16 +332,12 @@ std::vector<torch::Tensor> tconv_wgrad_v3(torch::Tensor dy, torch::Tensor x,
     case 3: LAUNCH_NT(NS_, 3, DET_); break;                                    \
     default: LAUNCH_NT(NS_, 4, DET_); break;                                   \
   }
-  if (nsub == 2) {
+  if (p.nsub == 2) {
     if (det) LAUNCH_NT_MT(2, true) else LAUNCH_NT_MT(2, false)
   } else {
     if (det) LAUNCH_NT_MT(1, true) else LAUNCH_NT_MT(1, false)
   }
 #undef LAUNCH_NT_MT
 #undef LAUNCH_NT
-  auto dw = torch::empty({T, F, C, 3, 3}, fopt);
-  launch_wgrad_finalize(acc.data_ptr<float>(), dw.data_ptr<float>(), T, F, C,
-                        nslices, stream.stream());
-  auto db = nslices == 1 ? dbacc.select(1, 0).contiguous() : dbacc.sum(1);
-  return {dw, db};
+  return finish_wgrad(acc, dbacc, T, F, C, p.nslices, stream.stream());
 }

@@ -5,8 +5,10 @@ through the inner-loop support forward):
 
 * the conv trio (fwd/dgrad/wgrad) is mutually bilinear — each backward
   composes the other two kernels, so convs run on custom kernels at every
-  derivative order; the stride-2 trio of the max_pooling=False backbone
-  (sconv.hip) is composed the same way;
+  derivative order.  There is one trio of Functions; a backend record
+  (``_ConvBackend``) names the kernels behind it: bf16 stride 1
+  (tconv.hip, wgrad_nt.hip, dconv.hip), bf16 stride 2 of the
+  max_pooling=False backbone (sconv.hip) and fp32 stride 1 (fconv.hip);
 * BN+act and softmax-CE make their *first backward* its own Function
   whose backward evaluates the analytic closed-form second derivative
   (bn_dbwd.hip / ce_dbwd) — also custom kernels at every order;
@@ -21,9 +23,9 @@ through the inner-loop support forward):
   individual Functions under create_graph.
 
 fp32 activations (``--compute_dtype fp32``, ``--fp32_support_pass``): the
-stride-1 conv trio runs on fconv.hip (exact fp32 MFMA, unrounded weights,
-ordered split-K wgrad) and the linear head on linear.hip's fp32
-instantiation, composed like their bf16 twins.  ``MAML355_FCONV=0``
+stride-1 convs take the fconv.hip backend (exact fp32 MFMA, unrounded
+weights, ordered split-K wgrad) and the linear head runs on linear.hip's
+fp32 instantiation, composed like its bf16 twin.  ``MAML355_FCONV=0``
 restores the grouped-ATen conv and ``torch.bmm`` for A/B runs.
 
 Convs with a stride other than 1 or 2, more than 64 channels, or fp32
@@ -33,6 +35,7 @@ warning.
 
 from __future__ import annotations
 
+import collections
 import os
 
 import torch
@@ -371,7 +374,105 @@ def lslr_update(arena, grad, lr_vec):
 # conv trio — MFMA implicit GEMM.  The three ops (fwd, dgrad, wgrad) are
 # mutually bilinear, so each backward is a composition of the other two:
 # custom kernels at EVERY derivative order (second-order MAML's
-# create_graph included), no torch fallback on the hot path.
+# create_graph included), no torch fallback on the hot path.  The
+# composition is written once; a backend record says which kernels run:
+#   fwd(x, w, b, pad, want_stats) -> (y, sums or None)
+#   dgrad(dy, w, pad, H, W) -> dx     (H, W explicit: under stride 2 two
+#                                      input sizes share one Ho)
+#   wgrad(dy, x, pad, with_bias) -> (dw, db)
+# ---------------------------------------------------------------------------
+_ConvBackend = collections.namedtuple("_ConvBackend", "fwd dgrad wgrad")
+
+
+class _ConvFwdFn(torch.autograd.Function):
+    """Returns (y, bn_sums): with want_stats the bf16 stride-1 epilogue
+    accumulates the following BN's per-channel sum/sum-of-squares for free;
+    the other backends return no sums (None)."""
+
+    @staticmethod
+    def forward(ctx, be, x, w, b, pad, want_stats):
+        ctx.save_for_backward(x, w)
+        ctx.be, ctx.pad = be, pad
+        ctx.has_bias = b is not None
+        y, sums = be.fwd(x, w, b, pad, want_stats)
+        if sums is not None:
+            ctx.mark_non_differentiable(sums)
+        return y, sums
+
+    @staticmethod
+    def backward(ctx, dy, dsums):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[1]:
+            dx = _ConvDgradFn.apply(ctx.be, dy, w, ctx.pad,
+                                    x.shape[2], x.shape[3])
+        if ctx.needs_input_grad[2]:
+            want_bias = ctx.has_bias and ctx.needs_input_grad[3]
+            dw, db = _ConvWgradFn.apply(ctx.be, dy, x, ctx.pad, want_bias)
+            if not want_bias:
+                db = None
+        elif ctx.has_bias and ctx.needs_input_grad[3]:
+            db = dy.float().sum(dim=(1, 2, 3))
+        return None, dx, dw, db, None, None
+
+
+def _conv_fwd(be, x, w, b, pad):
+    return _ConvFwdFn.apply(be, x, w, b, pad, False)[0]
+
+
+class _ConvDgradFn(torch.autograd.Function):
+    """dx = dgrad(dy, w) for an input of size (H, W)."""
+
+    @staticmethod
+    def forward(ctx, be, dy, w, pad, H, W):
+        ctx.save_for_backward(dy, w)
+        ctx.be, ctx.pad = be, pad
+        return be.dgrad(dy, w, pad, H, W)
+
+    @staticmethod
+    def backward(ctx, g):
+        dy, w = ctx.saved_tensors
+        g = g.contiguous()
+        d_dy = d_w = None
+        if ctx.needs_input_grad[1]:
+            d_dy = _conv_fwd(ctx.be, g, w, None, ctx.pad)
+        if ctx.needs_input_grad[2]:
+            d_w = _ConvWgradFn.apply(ctx.be, dy, g, ctx.pad, False)[0]
+        return None, d_dy, d_w, None, None, None
+
+
+class _ConvWgradFn(torch.autograd.Function):
+    """(dy, x) -> (dw, db); db is the fused bias gradient (sum of dy over
+    positions) — the wgrad kernel already stages the dY tiles, so the
+    reduction rides along instead of a separate big ATen sum."""
+
+    @staticmethod
+    def forward(ctx, be, dy, x, pad, with_bias):
+        ctx.save_for_backward(dy, x)
+        ctx.be, ctx.pad = be, pad
+        dw, db = be.wgrad(dy, x, pad, with_bias)
+        return dw, db
+
+    @staticmethod
+    def backward(ctx, gw, gdb):
+        dy, x = ctx.saved_tensors
+        d_dy = d_x = None
+        if ctx.needs_input_grad[1]:
+            if gw is not None:
+                d_dy = _conv_fwd(ctx.be, x, gw.contiguous(), None, ctx.pad)
+            if gdb is not None:
+                T, F = gdb.shape
+                add = gdb.view(T, 1, 1, 1, F).to(dy.dtype)
+                d_dy = add.expand_as(dy).contiguous() if d_dy is None else d_dy + add
+        if ctx.needs_input_grad[2] and gw is not None:
+            d_x = _ConvDgradFn.apply(ctx.be, dy, gw.contiguous(), ctx.pad,
+                                     x.shape[2], x.shape[3])
+        return None, d_dy, d_x, None, None
+
+
+# ---------------------------------------------------------------------------
+# backend: bf16 stride 1 — tconv.hip / wgrad_nt.hip / dconv.hip
 # ---------------------------------------------------------------------------
 def _dconv_ok(ci: int, f: int) -> bool:
     """Direct VALU conv for small input-channel counts (the first layer's
@@ -389,232 +490,94 @@ def _conv_v2_ok(ci: int) -> bool:
     return ci % 8 == 0 and os.environ.get("MAML355_CONV_V2", "1") != "0"
 
 
-class _ConvFwdFn(torch.autograd.Function):
-    """Returns (y, bn_sums): with want_stats the epilogue accumulates the
-    following BN's per-channel sum/sum-of-squares for free."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, pad, want_stats):
-        ctx.save_for_backward(x, w)
-        ctx.pad = pad
-        ctx.has_bias = b is not None
-        H, W = x.shape[2], x.shape[3]
-        Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
-        if _dconv_ok(x.shape[4], w.shape[1]):
-            # first-layer shapes: direct VALU conv (im2col-MFMA wastes
-            # >4x the MACs at K = 9..27)
-            y = _ext().dconv_fwd(x, w, b, pad, Ho, Wo)
-            sums = torch.empty(0, device=x.device, dtype=torch.float32)
-        elif _conv_v2_ok(x.shape[4]):
-            wp = _ext().tconv_repack_v2(w, False)
-            y, sums = _ext().tconv_mm_v2(x, wp, b, pad, Ho, Wo, w.shape[1],
-                                         want_stats)
-        else:
-            wp = _ext().tconv_repack(w, False)
-            y, sums = _ext().tconv_mm(x, wp, b, pad, Ho, Wo, want_stats)
-        ctx.mark_non_differentiable(sums)
-        return y, sums
-
-    @staticmethod
-    def backward(ctx, dy, dsums):
-        x, w = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _ConvDgradFn.apply(dy, w, ctx.pad)
-        if ctx.needs_input_grad[1]:
-            want_bias = ctx.has_bias and ctx.needs_input_grad[2]
-            dw, db = _ConvWgradFn.apply(dy, x, ctx.pad, want_bias)
-            if not want_bias:
-                db = None
-        elif ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy.float().sum(dim=(1, 2, 3))
-        return dx, dw, db, None, None
-
-
-def _conv_fwd(x, w, b, pad):
-    return _ConvFwdFn.apply(x, w, b, pad, False)[0]
-
-
-class _ConvDgradFn(torch.autograd.Function):
-    """dx = dgrad(dy, w): the fwd kernel run with flipped/transposed
-    repacked weights and pad' = 2 - pad (full-correlation identity)."""
-
-    @staticmethod
-    def forward(ctx, dy, w, pad):
-        ctx.save_for_backward(dy, w)
-        ctx.pad = pad
-        Ho, Wo = dy.shape[2], dy.shape[3]
-        H, W = Ho - 2 * pad + 2, Wo - 2 * pad + 2
-        if _conv_v2_ok(dy.shape[4]):
-            wp = _ext().tconv_repack_v2(w, True)
-            return _ext().tconv_mm_v2(dy, wp, None, 2 - pad, H, W,
-                                      w.shape[2], False)[0]
-        wp = _ext().tconv_repack(w, True)
-        return _ext().tconv_mm(dy, wp, None, 2 - pad, H, W, False)[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        dy, w = ctx.saved_tensors
-        g = g.contiguous()
-        d_dy = d_w = None
-        if ctx.needs_input_grad[0]:
-            d_dy = _conv_fwd(g, w, None, ctx.pad)
-        if ctx.needs_input_grad[1]:
-            d_w = _ConvWgradFn.apply(dy, g, ctx.pad, False)[0]
-        return d_dy, d_w, None
-
-
-# v3 has no fixed-cost operand copies, so unlike v2 it needs no lower bound
-# on the reduction length: measured at or ahead of v1 down to the smallest
-# workload shapes (profiles/README.md, "wgrad v3").
-_WGRAD_V3_MIN_POSITIONS = 0
-
-
-def _wgrad_v3_ok(c: int, f: int, positions: int) -> bool:
+def _wgrad_v3_ok(c: int, f: int) -> bool:
     """Transpose-free wgrad (wgrad_nt.hip): 8-aligned F <= 64, 8-aligned C
-    or the first layer's C in {1, 3}.  MAML355_WGRAD_V3=0 restores the
-    v2 / v1 routing below."""
+    or the first layer's C in {1, 3}.  It has no fixed-cost operand copies,
+    so unlike v2 it needs no lower bound on the reduction length (measured
+    at or ahead of v1 down to the smallest workload shapes,
+    profiles/README.md, "wgrad v3").  MAML355_WGRAD_V3=0 restores the
+    v2 / v1 routing."""
     return (f % 8 == 0 and f <= 64 and (c % 8 == 0 or c in (1, 3))
-            and positions >= _WGRAD_V3_MIN_POSITIONS
             and os.environ.get("MAML355_WGRAD_V3", "1") != "0")
 
 
-class _ConvWgradFn(torch.autograd.Function):
-    """(dy, x) -> (dw, db); db is the fused bias gradient (sum of dy over
-    positions) — the wgrad kernel already stages the dY tiles, so the
-    reduction rides along instead of a separate big ATen sum."""
-
-    @staticmethod
-    def forward(ctx, dy, x, pad, with_bias):
-        ctx.save_for_backward(dy, x)
-        ctx.pad = pad
-        # v2 (global transposes -> linear async staging, any Wo incl. the
-        # first layer); v1 for F > 64.  The direct VALU wgrad
-        # (dconv_wgrad) measured 2.3x SLOWER than v2 at the conv0 shape
-        # (serial position walk per wave) — opt-in only.
-        if (x.shape[4] <= 8 and dy.shape[4] <= 64
-                and os.environ.get("MAML355_DCONV_WGRAD", "0") == "1"):
-            dw, db = _ext().dconv_wgrad(dy, x, pad, with_bias)
-        elif _wgrad_v3_ok(x.shape[4], dy.shape[4],
-                          dy.shape[1] * dy.shape[2] * dy.shape[3]):
-            # v3: both operands staged as stored, the transpose moved into
-            # the LDS read — none of v2's operand copies
-            dw, db = _ext().tconv_wgrad_v3(dy, x, pad, with_bias)
-        elif (dy.shape[4] <= 64
-                and dy.shape[1] * dy.shape[2] * dy.shape[3] >= 30000
-                and os.environ.get("MAML355_WGRAD_V2", "1") != "0"):
-            # v2's operand transposes are fixed cost: below ~30k reduction
-            # positions the v1 gather kernel wins (measured on the
-            # omniglot target passes: whole-bench +3% with v1 there)
-            dw, db = _ext().tconv_wgrad_v2(dy, x, pad, with_bias)
-        else:
-            dw, db = _ext().tconv_wgrad(dy, x, pad, with_bias)
-        return dw, db
-
-    @staticmethod
-    def backward(ctx, gw, gdb):
-        dy, x = ctx.saved_tensors
-        d_dy = d_x = None
-        if ctx.needs_input_grad[0]:
-            if gw is not None:
-                d_dy = _conv_fwd(x, gw.contiguous(), None, ctx.pad)
-            if gdb is not None:
-                T, F = gdb.shape
-                add = gdb.view(T, 1, 1, 1, F).to(dy.dtype)
-                d_dy = add.expand_as(dy).contiguous() if d_dy is None else d_dy + add
-        if ctx.needs_input_grad[1] and gw is not None:
-            d_x = _ConvDgradFn.apply(dy, gw.contiguous(), ctx.pad)
-        return d_dy, d_x, None, None
+def _tconv_fwd(x, w, b, pad, want_stats):
+    H, W = x.shape[2], x.shape[3]
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    if _dconv_ok(x.shape[4], w.shape[1]):
+        # first-layer shapes: direct VALU conv (im2col-MFMA wastes
+        # >4x the MACs at K = 9..27)
+        y = _ext().dconv_fwd(x, w, b, pad, Ho, Wo)
+        return y, torch.empty(0, device=x.device, dtype=torch.float32)
+    if _conv_v2_ok(x.shape[4]):
+        wp = _ext().tconv_repack_v2(w, False)
+        return _ext().tconv_mm_v2(x, wp, b, pad, Ho, Wo, w.shape[1],
+                                  want_stats)
+    wp = _ext().tconv_repack(w, False)
+    return _ext().tconv_mm(x, wp, b, pad, Ho, Wo, want_stats)
 
 
-# ---------------------------------------------------------------------------
-# stride-2 conv trio (max_pooling=False backbone) — sconv.hip.  Composed
-# exactly like the stride-1 trio above: mutually bilinear, each backward
-# calls the other two, custom kernels at every derivative order.  dgrad
-# carries (H, W) explicitly: two input sizes share one Ho under stride 2.
-# ---------------------------------------------------------------------------
-class _SConvFwdFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, b, pad):
-        ctx.save_for_backward(x, w)
-        ctx.pad = pad
-        ctx.has_bias = b is not None
-        wp = _ext().sconv_repack(w, False)
-        return _ext().sconv_fwd(x, wp, b, pad)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _SConvDgradFn.apply(dy, w, ctx.pad, x.shape[2], x.shape[3])
-        if ctx.needs_input_grad[1]:
-            want_bias = ctx.has_bias and ctx.needs_input_grad[2]
-            dw, db = _SConvWgradFn.apply(dy, x, ctx.pad, want_bias)
-            if not want_bias:
-                db = None
-        elif ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy.float().sum(dim=(1, 2, 3))
-        return dx, dw, db, None
+def _tconv_dgrad(dy, w, pad, H, W):
+    """The fwd kernel run with flipped/transposed repacked weights and
+    pad' = 2 - pad (full-correlation identity)."""
+    if _conv_v2_ok(dy.shape[4]):
+        wp = _ext().tconv_repack_v2(w, True)
+        return _ext().tconv_mm_v2(dy, wp, None, 2 - pad, H, W,
+                                  w.shape[2], False)[0]
+    wp = _ext().tconv_repack(w, True)
+    return _ext().tconv_mm(dy, wp, None, 2 - pad, H, W, False)[0]
 
 
-class _SConvDgradFn(torch.autograd.Function):
-    """dx = dgrad_s2(dy, w): four parity sub-GEMMs in one launch."""
+def _tconv_wgrad(dy, x, pad, with_bias):
+    # The direct VALU wgrad (dconv_wgrad) measured 2.3x SLOWER than v2 at
+    # the conv0 shape (serial position walk per wave) — opt-in only.
+    if (x.shape[4] <= 8 and dy.shape[4] <= 64
+            and os.environ.get("MAML355_DCONV_WGRAD", "0") == "1"):
+        return _ext().dconv_wgrad(dy, x, pad, with_bias)
+    if _wgrad_v3_ok(x.shape[4], dy.shape[4]):
+        # v3: both operands staged as stored, the transpose moved into
+        # the LDS read — none of v2's operand copies
+        return _ext().tconv_wgrad_v3(dy, x, pad, with_bias)
+    if (dy.shape[4] <= 64
+            and dy.shape[1] * dy.shape[2] * dy.shape[3] >= 30000
+            and os.environ.get("MAML355_WGRAD_V2", "1") != "0"):
+        # v2 (global transposes -> linear async staging, any Wo).  Its
+        # operand transposes are fixed cost: below ~30k reduction
+        # positions the v1 gather kernel wins (measured on the omniglot
+        # target passes: whole-bench +3% with v1 there)
+        return _ext().tconv_wgrad_v2(dy, x, pad, with_bias)
+    return _ext().tconv_wgrad(dy, x, pad, with_bias)
 
-    @staticmethod
-    def forward(ctx, dy, w, pad, H, W):
-        ctx.save_for_backward(dy, w)
-        ctx.pad = pad
-        wp = _ext().sconv_repack(w, True)
-        return _ext().sconv_dgrad(dy, wp, pad, H, W)
 
-    @staticmethod
-    def backward(ctx, g):
-        dy, w = ctx.saved_tensors
-        g = g.contiguous()
-        d_dy = d_w = None
-        if ctx.needs_input_grad[0]:
-            d_dy = _SConvFwdFn.apply(g, w, None, ctx.pad)
-        if ctx.needs_input_grad[1]:
-            d_w = _SConvWgradFn.apply(dy, g, ctx.pad, False)[0]
-        return d_dy, d_w, None, None, None
-
-
-class _SConvWgradFn(torch.autograd.Function):
-    """(dy, x) -> (dw, db) with the bias gradient fused, as _ConvWgradFn."""
-
-    @staticmethod
-    def forward(ctx, dy, x, pad, with_bias):
-        ctx.save_for_backward(dy, x)
-        ctx.pad = pad
-        dw, db = _ext().sconv_wgrad(dy, x, pad, with_bias)
-        return dw, db
-
-    @staticmethod
-    def backward(ctx, gw, gdb):
-        dy, x = ctx.saved_tensors
-        d_dy = d_x = None
-        if ctx.needs_input_grad[0]:
-            if gw is not None:
-                d_dy = _SConvFwdFn.apply(x, gw.contiguous(), None, ctx.pad)
-            if gdb is not None:
-                T, F = gdb.shape
-                add = gdb.view(T, 1, 1, 1, F).to(dy.dtype)
-                d_dy = add.expand_as(dy).contiguous() if d_dy is None else d_dy + add
-        if ctx.needs_input_grad[1] and gw is not None:
-            d_x = _SConvDgradFn.apply(dy, gw.contiguous(), ctx.pad,
-                                      x.shape[2], x.shape[3])
-        return d_dy, d_x, None, None
+_TCONV = _ConvBackend(_tconv_fwd, _tconv_dgrad, _tconv_wgrad)
 
 
 # ---------------------------------------------------------------------------
-# fp32 stride-1 conv trio — fconv.hip.  Composed exactly like the bf16 trio
-# above: mutually bilinear, each backward calls the other two, the fused db
-# carries its second-order term.  Weights are used unrounded; C and F are
-# any value in 1..64 (no channel padding); wgrad is always the ordered
-# private-slice reduction, so the trio is bitwise reproducible in every mode.
+# backend: bf16 stride 2 (max_pooling=False backbone) — sconv.hip.  dgrad is
+# four parity sub-GEMMs in one launch.  No BN-stats epilogue.
+# ---------------------------------------------------------------------------
+def _sconv_fwd(x, w, b, pad, want_stats):
+    wp = _ext().sconv_repack(w, False)
+    return _ext().sconv_fwd(x, wp, b, pad), None
+
+
+def _sconv_dgrad(dy, w, pad, H, W):
+    wp = _ext().sconv_repack(w, True)
+    return _ext().sconv_dgrad(dy, wp, pad, H, W)
+
+
+def _sconv_wgrad(dy, x, pad, with_bias):
+    return _ext().sconv_wgrad(dy, x, pad, with_bias)
+
+
+_SCONV = _ConvBackend(_sconv_fwd, _sconv_dgrad, _sconv_wgrad)
+
+
+# ---------------------------------------------------------------------------
+# backend: fp32 stride 1 — fconv.hip.  Weights are used unrounded; C and F
+# are any value in 1..64 (no channel padding); wgrad is always the ordered
+# private-slice reduction, so the trio is bitwise reproducible in every
+# mode.  No BN-stats epilogue.
 # ---------------------------------------------------------------------------
 def _fconv_on() -> bool:
     """MAML355_FCONV=0 restores the pre-kernel fp32 behaviour (grouped-ATen
@@ -622,82 +585,23 @@ def _fconv_on() -> bool:
     return os.environ.get("MAML355_FCONV", "1") != "0"
 
 
-class _FConvFwdFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, b, pad):
-        ctx.save_for_backward(x, w)
-        ctx.pad = pad
-        ctx.has_bias = b is not None
-        H, W = x.shape[2], x.shape[3]
-        wp = _ext().fconv_repack(w, False)
-        return _ext().fconv_mm(x, wp, b, pad, H + 2 * pad - 2, W + 2 * pad - 2)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _FConvDgradFn.apply(dy, w, ctx.pad)
-        if ctx.needs_input_grad[1]:
-            want_bias = ctx.has_bias and ctx.needs_input_grad[2]
-            dw, db = _FConvWgradFn.apply(dy, x, ctx.pad, want_bias)
-            if not want_bias:
-                db = None
-        elif ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy.sum(dim=(1, 2, 3))
-        return dx, dw, db, None
+def _fconv_fwd(x, w, b, pad, want_stats):
+    H, W = x.shape[2], x.shape[3]
+    wp = _ext().fconv_repack(w, False)
+    return _ext().fconv_mm(x, wp, b, pad, H + 2 * pad - 2, W + 2 * pad - 2), None
 
 
-class _FConvDgradFn(torch.autograd.Function):
-    """dx = dgrad(dy, w): fconv_mm with flipped/transposed repacked weights
-    and pad' = 2 - pad."""
-
-    @staticmethod
-    def forward(ctx, dy, w, pad):
-        ctx.save_for_backward(dy, w)
-        ctx.pad = pad
-        Ho, Wo = dy.shape[2], dy.shape[3]
-        wp = _ext().fconv_repack(w, True)
-        return _ext().fconv_mm(dy, wp, None, 2 - pad,
-                               Ho - 2 * pad + 2, Wo - 2 * pad + 2)
-
-    @staticmethod
-    def backward(ctx, g):
-        dy, w = ctx.saved_tensors
-        g = g.contiguous()
-        d_dy = d_w = None
-        if ctx.needs_input_grad[0]:
-            d_dy = _FConvFwdFn.apply(g, w, None, ctx.pad)
-        if ctx.needs_input_grad[1]:
-            d_w = _FConvWgradFn.apply(dy, g, ctx.pad, False)[0]
-        return d_dy, d_w, None
+def _fconv_dgrad(dy, w, pad, H, W):
+    """fconv_mm with flipped/transposed repacked weights and pad' = 2 - pad."""
+    wp = _ext().fconv_repack(w, True)
+    return _ext().fconv_mm(dy, wp, None, 2 - pad, H, W)
 
 
-class _FConvWgradFn(torch.autograd.Function):
-    """(dy, x) -> (dw, db) with the bias gradient fused, as _ConvWgradFn."""
+def _fconv_wgrad(dy, x, pad, with_bias):
+    return _ext().fconv_wgrad(dy, x, pad, with_bias)
 
-    @staticmethod
-    def forward(ctx, dy, x, pad, with_bias):
-        ctx.save_for_backward(dy, x)
-        ctx.pad = pad
-        dw, db = _ext().fconv_wgrad(dy, x, pad, with_bias)
-        return dw, db
 
-    @staticmethod
-    def backward(ctx, gw, gdb):
-        dy, x = ctx.saved_tensors
-        d_dy = d_x = None
-        if ctx.needs_input_grad[0]:
-            if gw is not None:
-                d_dy = _FConvFwdFn.apply(x, gw.contiguous(), None, ctx.pad)
-            if gdb is not None:
-                T, F = gdb.shape
-                add = gdb.view(T, 1, 1, 1, F).to(dy.dtype)
-                d_dy = add.expand_as(dy).contiguous() if d_dy is None else d_dy + add
-        if ctx.needs_input_grad[1] and gw is not None:
-            d_x = _FConvDgradFn.apply(dy, gw.contiguous(), ctx.pad)
-        return d_dy, d_x, None, None
+_FCONV = _ConvBackend(_fconv_fwd, _fconv_dgrad, _fconv_wgrad)
 
 
 _FALLBACK_WARNED = set()
@@ -720,9 +624,9 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
         # fp32 activations: the fp32 MFMA trio, weights and bias unrounded.
         # No BN-stats epilogue: return_stats yields empty sums and the BN
         # kernels compute their own statistics, as on the stride-2 path.
-        y = _FConvFwdFn.apply(x.contiguous(), w.float().contiguous(),
-                              b.float().contiguous() if b is not None else None,
-                              padding)
+        y = _ConvFwdFn.apply(_FCONV, x.contiguous(), w.float().contiguous(),
+                             b.float().contiguous() if b is not None else None,
+                             padding, False)[0]
         if return_stats:
             return y, torch.empty(0, device=x.device, dtype=torch.float32)
         return y
@@ -749,9 +653,9 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
         if C < 8:
             x = torch.nn.functional.pad(x, (0, 8 - C))
             w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 8 - C))
-        y = _SConvFwdFn.apply(x.contiguous(), w.contiguous(),
-                              b.contiguous() if b is not None else None,
-                              padding)
+        y = _ConvFwdFn.apply(_SCONV, x.contiguous(), w.contiguous(),
+                             b.contiguous() if b is not None else None,
+                             padding, False)[0]
         return (y, None) if return_stats else y
     if C < 8 and not _dconv_ok(C, F):
         # small C without a direct-kernel instantiation: zero-pad to 8 so
@@ -759,7 +663,7 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
         # differentiable, so dw/dx slicing back to C channels is automatic.
         x = torch.nn.functional.pad(x, (0, 8 - C))
         w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 8 - C))
-    y, sums = _ConvFwdFn.apply(x.contiguous(), w.contiguous(),
+    y, sums = _ConvFwdFn.apply(_TCONV, x.contiguous(), w.contiguous(),
                                b.contiguous() if b is not None else None,
                                padding, return_stats)
     return (y, sums) if return_stats else y
