@@ -21,6 +21,7 @@ std::vector<torch::Tensor> bn_act_pool_bwd(torch::Tensor dyp, torch::Tensor mask
 // pool.hip
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor x);
 torch::Tensor maxpool2x2_bwd(torch::Tensor dy, torch::Tensor mask, long H, long W);
+torch::Tensor maxpool2x2_gather(torch::Tensor x, torch::Tensor mask);
 // softmax_ce.hip
 std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor labels);
 torch::Tensor ce_bwd(torch::Tensor probs, torch::Tensor labels, torch::Tensor gtask);
@@ -32,6 +33,11 @@ std::vector<torch::Tensor> bn_act_dbwd(torch::Tensor x, torch::Tensor u,
                                        torch::Tensor rstd, torch::Tensor gamma,
                                        torch::Tensor beta, torch::Tensor ggam,
                                        torch::Tensor gbet, double slope, bool act);
+std::vector<torch::Tensor> bn_act_dbwd_full(
+    torch::Tensor x, torch::Tensor u, torch::Tensor gx, torch::Tensor mean,
+    torch::Tensor rstd, torch::Tensor gamma, torch::Tensor beta,
+    c10::optional<torch::Tensor> ggam, c10::optional<torch::Tensor> gbet,
+    double slope, bool act);
 // layernorm.hip
 std::vector<torch::Tensor> ln_act_fwd(torch::Tensor x, torch::Tensor bias,
                                       double eps, double slope, bool act);
@@ -109,9 +115,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_act_pool_bwd", &bn_act_pool_bwd, "fused BN+leakyReLU+maxpool bwd");
   m.def("maxpool2x2_fwd", &maxpool2x2_fwd, "NHWC maxpool 2x2 fwd");
   m.def("maxpool2x2_bwd", &maxpool2x2_bwd, "NHWC maxpool 2x2 bwd");
+  m.def("maxpool2x2_gather", &maxpool2x2_gather,
+        "NHWC 2x2 window gather through a saved argmax mask");
   m.def("ce_fwd", &ce_fwd, "fused softmax-CE fwd");
   m.def("ce_dbwd", &ce_dbwd, "softmax-CE double-backward");
   m.def("bn_act_dbwd", &bn_act_dbwd, "BN+leakyReLU analytic double-backward");
+  m.def("bn_act_dbwd_full", &bn_act_dbwd_full,
+        "BN+leakyReLU double-backward with d_gamma_t, optional ggam/gbet");
   m.def("ce_bwd", &ce_bwd, "fused softmax-CE bwd");
   m.def("ln_act_fwd", &ln_act_fwd, "fused task-batched LayerNorm+bias+leakyReLU fwd");
   m.def("ln_act_bwd", &ln_act_bwd, "fused task-batched LayerNorm+bias+leakyReLU bwd");

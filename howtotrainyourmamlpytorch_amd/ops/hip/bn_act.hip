@@ -72,21 +72,43 @@ __global__ void bn_sums_vec_kernel(const scalar_t* __restrict__ x,
   }
 }
 
-// ordered reduction of partials[T, NBLK, 2, C] -> sums[T, 2, C]
+// ordered reduction of partials[T, NBLK, 2, C] -> sums[T, 2, C].  The
+// loads of kAhead2 blocks are issued together and then added in ascending
+// block order: still one serial chain of additions per (t, c), so the bits
+// are those of the one-load-one-add loop; only the load latency overlaps.
+// out0 / out1 ([T, C], may be null) receive the two rows as tensors of
+// their own (the backward's dbeta_t / dgamma_t).
+constexpr int kAhead2 = 16;
 __global__ void bn_reduce2_kernel(const float* __restrict__ partials,
                                   float* __restrict__ sums, int T, int nblk,
-                                  int C) {
+                                  int C, float* __restrict__ out0,
+                                  float* __restrict__ out1) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= T * C) return;
   const int t = i / C, c = i % C;
   float s = 0.f, q = 0.f;
-  for (int b = 0; b < nblk; ++b) {
-    const float* p = partials + (((long)t * nblk + b) * 2) * C;
-    s += p[c];
-    q += p[C + c];
+  for (int b0 = 0; b0 < nblk; b0 += kAhead2) {
+    float vs[kAhead2], vq[kAhead2];
+#pragma unroll
+    for (int a = 0; a < kAhead2; ++a) {
+      if (b0 + a < nblk) {
+        const float* p = partials + (((long)t * nblk + b0 + a) * 2) * C;
+        vs[a] = p[c];
+        vq[a] = p[C + c];
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < kAhead2; ++a) {
+      if (b0 + a < nblk) {
+        s += vs[a];
+        q += vq[a];
+      }
+    }
   }
   sums[((long)t * 2 + 0) * C + c] = s;
   sums[((long)t * 2 + 1) * C + c] = q;
+  if (out0 != nullptr) out0[i] = s;
+  if (out1 != nullptr) out1[i] = q;
 }
 
 template <typename scalar_t, bool PER_TASK_AFFINE, bool ACT>
@@ -671,6 +693,9 @@ namespace {
 constexpr int kRowsPerBlock = 256;
 constexpr int kThreads = 256;
 
+// the 8-channel vector kernels; their ordered reduce writes the sums whole
+inline bool bn_vec_ok(int C) { return (C % 8 == 0) && C <= 512; }
+
 template <typename scalar_t>
 void bn_fwd_impl(const torch::Tensor& x, const torch::Tensor& gamma,
                  const torch::Tensor& beta, torch::Tensor& y,
@@ -679,7 +704,7 @@ void bn_fwd_impl(const torch::Tensor& x, const torch::Tensor& gamma,
                  int T, long M, int C) {
   auto stream = at::cuda::getCurrentCUDAStream();
   const bool per_task = gamma.dim() == 2;
-  const bool vec = (C % 8 == 0) && C <= 512;
+  const bool vec = bn_vec_ok(C);
   const int cpad = ((C + WAVE - 1) / WAVE) * WAVE;
   dim3 sums_grid(T, (unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock));
   const int threads = cpad * std::max<int>(1, kThreads / cpad);
@@ -696,7 +721,8 @@ void bn_fwd_impl(const torch::Tensor& x, const torch::Tensor& gamma,
                        partials.data_ptr<float>(), T, M, C, rpb);
     hipLaunchKernelGGL(bn_reduce2_kernel, dim3((T * C + 255) / 256), dim3(256),
                        0, stream.stream(), partials.data_ptr<float>(),
-                       sums.data_ptr<float>(), T, nb, C);
+                       sums.data_ptr<float>(), T, nb, C, (float*)nullptr,
+                       (float*)nullptr);
   } else
   hipLaunchKernelGGL((bn_sums_kernel<scalar_t>), sums_grid, dim3(threads),
                      lds_bytes, stream.stream(),
@@ -739,11 +765,12 @@ template <typename scalar_t>
 void bn_bwd_impl(const torch::Tensor& dy, const torch::Tensor& x,
                  const torch::Tensor& mean, const torch::Tensor& rstd,
                  const torch::Tensor& gamma, const torch::Tensor& beta,
-                 torch::Tensor& bsums, torch::Tensor& dx, double slope,
+                 torch::Tensor& bsums, torch::Tensor& dx,
+                 torch::Tensor& dgamma_t, torch::Tensor& dbeta_t, double slope,
                  bool act, int T, long M, int C) {
   auto stream = at::cuda::getCurrentCUDAStream();
   const bool per_task = gamma.dim() == 2;
-  const bool vec = (C % 8 == 0) && C <= 512;
+  const bool vec = bn_vec_ok(C);
   const int cpad = ((C + WAVE - 1) / WAVE) * WAVE;
   dim3 sums_grid(T, (unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock));
   const int threads = cpad * std::max<int>(1, kThreads / cpad);
@@ -768,7 +795,9 @@ void bn_bwd_impl(const torch::Tensor& dy, const torch::Tensor& x,
       hipLaunchKernelGGL(bn_reduce2_kernel, dim3((T * C + 255) / 256),         \
                          dim3(256), 0, stream.stream(),                        \
                          partials.data_ptr<float>(),                           \
-                         bsums.data_ptr<float>(), T, nb, C);                   \
+                         bsums.data_ptr<float>(), T, nb, C,                    \
+                         dbeta_t.data_ptr<float>(),                            \
+                         dgamma_t.data_ptr<float>());                          \
       hipLaunchKernelGGL((bn_bwd_dx_vec_kernel<scalar_t, PT, ACT_>),           \
                          sums_grid, dim3(256), 0, stream.stream(),             \
                          reinterpret_cast<const scalar_t*>(dy.data_ptr()),     \
@@ -815,7 +844,10 @@ std::vector<torch::Tensor> bn_act_fwd(torch::Tensor x, torch::Tensor gamma,
   const long M = x.size(1);
   const int C = (int)x.size(2);
   auto opts = x.options().dtype(torch::kFloat32);
-  auto sums = torch::zeros({T, 2, C}, opts);
+  // the scalar path accumulates into sums with atomics; the vector path's
+  // ordered reduce overwrites it whole
+  auto sums = bn_vec_ok(C) ? torch::empty({T, 2, C}, opts)
+                           : torch::zeros({T, 2, C}, opts);
   auto mean = torch::empty({T, C}, opts);
   auto var = torch::empty({T, C}, opts);
   auto rstd = torch::empty({T, C}, opts);
@@ -842,19 +874,30 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy, torch::Tensor x,
   const long M = x.size(1);
   const int C = (int)x.size(2);
   auto opts = x.options().dtype(torch::kFloat32);
-  auto bsums = torch::zeros({T, 2, C}, opts);
+  const bool vec = bn_vec_ok(C);
+  auto bsums = vec ? torch::empty({T, 2, C}, opts)
+                   : torch::zeros({T, 2, C}, opts);
+  // vector path: the ordered reduce writes both straight into these
+  torch::Tensor dgamma_t, dbeta_t;
+  if (vec) {
+    dgamma_t = torch::empty({T, C}, opts);
+    dbeta_t = torch::empty({T, C}, opts);
+  }
   auto dx = torch::empty_like(x);
   auto gc = gamma.contiguous().to(torch::kFloat32);
   auto bc = beta.contiguous().to(torch::kFloat32);
   if (x.scalar_type() == torch::kFloat32) {
-    bn_bwd_impl<float>(dyc, x, mean, rstd, gc, bc, bsums, dx, slope, act, T, M, C);
+    bn_bwd_impl<float>(dyc, x, mean, rstd, gc, bc, bsums, dx, dgamma_t,
+                       dbeta_t, slope, act, T, M, C);
   } else if (x.scalar_type() == torch::kBFloat16) {
-    bn_bwd_impl<__hip_bfloat16>(dyc, x, mean, rstd, gc, bc, bsums, dx, slope, act, T, M, C);
+    bn_bwd_impl<__hip_bfloat16>(dyc, x, mean, rstd, gc, bc, bsums, dx,
+                                dgamma_t, dbeta_t, slope, act, T, M, C);
   } else {
     TORCH_CHECK(false, "bn_act_bwd: unsupported dtype");
   }
   // dbeta = bsums[:,0,:], dgamma = bsums[:,1,:]  (per task; wrapper reduces
   // over T when gamma is shared)
+  if (vec) return {dx, dgamma_t, dbeta_t};
   return {dx, bsums.select(1, 1).clone(), bsums.select(1, 0).clone()};
 }
 
@@ -875,7 +918,7 @@ std::vector<torch::Tensor> bn_act_pool_fwd(torch::Tensor x, torch::Tensor gamma,
   auto fopts = x.options().dtype(torch::kFloat32);
   const bool have_sums = sums_in.has_value() && sums_in->numel() == T * 2 * C;
   auto sums = have_sums ? sums_in->contiguous()
-                        : torch::zeros({T, 2, C}, fopts);
+                        : torch::empty({T, 2, C}, fopts);
   auto mean = torch::empty({T, C}, fopts);
   auto var = torch::empty({T, C}, fopts);
   auto rstd = torch::empty({T, C}, fopts);
@@ -902,7 +945,8 @@ std::vector<torch::Tensor> bn_act_pool_fwd(torch::Tensor x, torch::Tensor gamma,
       hipLaunchKernelGGL(bn_reduce2_kernel, dim3((T * C + 255) / 256),         \
                          dim3(256), 0, stream.stream(),                        \
                          partials.data_ptr<float>(),                           \
-                         sums.data_ptr<float>(), T, nb_, C);                   \
+                         sums.data_ptr<float>(), T, nb_, C, (float*)nullptr,   \
+                         (float*)nullptr);                                     \
     }                                                                          \
     const int fin_blocks = (T * C + 255) / 256;                                \
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(fin_blocks), dim3(256), 0,     \
@@ -943,7 +987,9 @@ std::vector<torch::Tensor> bn_act_pool_bwd(torch::Tensor dyp, torch::Tensor mask
   TORCH_CHECK(C % 8 == 0 && C <= 512);
   const long M = (long)NB * H * W;
   auto fopts = x.options().dtype(torch::kFloat32);
-  auto bsums = torch::zeros({T, 2, C}, fopts);
+  auto bsums = torch::empty({T, 2, C}, fopts);
+  auto dgamma_t = torch::empty({T, C}, fopts);
+  auto dbeta_t = torch::empty({T, C}, fopts);
   auto dx = torch::empty_like(x);
   auto gc = gamma.contiguous().to(torch::kFloat32);
   auto bc = beta.contiguous().to(torch::kFloat32);
@@ -969,7 +1015,9 @@ std::vector<torch::Tensor> bn_act_pool_bwd(torch::Tensor dyp, torch::Tensor mask
     hipLaunchKernelGGL(bn_reduce2_kernel, dim3((T * C + 255) / 256),           \
                        dim3(256), 0, stream.stream(),                          \
                        partials.data_ptr<float>(),                             \
-                       bsums.data_ptr<float>(), T, nb_, C);                    \
+                       bsums.data_ptr<float>(), T, nb_, C,                     \
+                       dbeta_t.data_ptr<float>(),                              \
+                       dgamma_t.data_ptr<float>());                            \
     hipLaunchKernelGGL((bn_pool_bwd_dx_vec_kernel<ST, PT>), g, dim3(256), 0,   \
                        stream.stream(),                                        \
                        reinterpret_cast<const ST*>(dypc.data_ptr()),           \
@@ -991,6 +1039,6 @@ std::vector<torch::Tensor> bn_act_pool_bwd(torch::Tensor dyp, torch::Tensor mask
     TORCH_CHECK(false, "bn_act_pool_bwd: unsupported dtype");
   }
 #undef LAUNCH_BPB
-  // dbeta_t = bsums[:,0], dgamma_t = bsums[:,1]
-  return {dx, bsums.select(1, 1).clone(), bsums.select(1, 0).clone()};
+  // dbeta_t = bsums[:,0], dgamma_t = bsums[:,1], written by the reduce
+  return {dx, dgamma_t, dbeta_t};
 }

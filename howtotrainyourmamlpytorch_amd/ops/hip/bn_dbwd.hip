@@ -96,21 +96,55 @@ __global__ void bn_dbwd_sums_kernel(const scalar_t* __restrict__ x,
 }
 
 // ordered reduction of partials[T, NBLK, 5, C] -> sums[T, 5, C]
-// (bitwise run-to-run deterministic; no global atomics)
-__global__ void bn_reduce5_kernel(const float* __restrict__ partials,
-                                  float* __restrict__ sums, int T, int nblk,
-                                  int C) {
+// (bitwise run-to-run deterministic; no global atomics).  The loads of
+// kAhead5 blocks are issued together and then added in ascending block
+// order: one serial chain of additions per (t, c), as before — only the
+// load latency overlaps.
+// With dgamma_t != nullptr the thread also finishes
+//   d_gamma_t = rstd * M * (Gu - s1*G - s2*Gxh)          (means over M)
+// with the operations, and the order, of the tensor expression it replaces
+// (s = sums * (1/M); rstd * M; s4 - s0*s2 - s1*s3; product), each rounded
+// on its own: contraction is off for those lines.
+constexpr int kAhead5 = 8;
+__global__ void __launch_bounds__(256)
+bn_reduce5_kernel(const float* __restrict__ partials, float* __restrict__ sums,
+                  int T, int nblk, int C, const float* __restrict__ rstd,
+                  float* __restrict__ dgamma_t, float Mf, float invM) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= T * C) return;
   const int t = i / C, c = i % C;
   float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int b = 0; b < nblk; ++b) {
-    const float* p = partials + (((long)t * nblk + b) * 5) * C;
+  for (int b0 = 0; b0 < nblk; b0 += kAhead5) {
+    float v[kAhead5][5];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) acc[k] += p[k * C + c];
+    for (int a = 0; a < kAhead5; ++a) {
+      if (b0 + a < nblk) {
+        const float* p = partials + (((long)t * nblk + b0 + a) * 5) * C;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) v[a][k] = p[k * C + c];
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < kAhead5; ++a) {
+      if (b0 + a < nblk) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) acc[k] += v[a][k];
+      }
+    }
   }
 #pragma unroll
   for (int k = 0; k < 5; ++k) sums[((long)t * 5 + k) * C + c] = acc[k];
+  if (dgamma_t != nullptr) {
+#pragma clang fp contract(off)
+    const float s0 = acc[0] * invM, s1 = acc[1] * invM, s2 = acc[2] * invM,
+                s3 = acc[3] * invM, s4 = acc[4] * invM;
+    const float rm = rstd[i] * Mf;
+    const float p02 = s0 * s2;
+    const float d1 = s4 - p02;
+    const float p13 = s1 * s3;
+    const float d2 = d1 - p13;
+    dgamma_t[i] = rm * d2;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -175,20 +209,123 @@ constexpr int kRowsPerBlockD = 256;
 constexpr int kThreadsD = 256;
 }  // namespace
 
-// returns {d_u, d_x, sums[T,5,C]} — d_gamma_t is finished by the wrapper:
-//   d_gamma_t = rstd * (Gu_sum - s1m*G_sum... see hip_autograd (cheap [T,C]).
-std::vector<torch::Tensor> bn_act_dbwd(torch::Tensor x, torch::Tensor u,
-                                       torch::Tensor gx, torch::Tensor mean,
-                                       torch::Tensor rstd, torch::Tensor gamma,
-                                       torch::Tensor beta, torch::Tensor ggam,
-                                       torch::Tensor gbet, double slope,
-                                       bool act) {
+// ---------------------------------------------------------------------------
+// pass 1, 8 channels per thread (16-byte loads for bf16), C % 8 == 0.
+//
+// The partials are bit-for-bit those of bn_dbwd_sums_kernel: partial
+// (t, slice, c) covers rows [256*slice, 256*slice + 256) and is the serial
+// sum over rgroup = 0..R-1 of the serial ascending sum over the rows
+// m = 256*slice + rgroup + R*k, with R that kernel's row groups per block
+// (4 for C <= 64).  Here a thread owns one (slice, rgroup) chain for 8
+// channels and a block owns several slices; which addends enter which chain,
+// and in what order, is unchanged.
+//
+// The per-element operations are pinned to the ones the compiler chose for
+// the scalar kernel (its pairing of G with s2 leaves s2's product unfused,
+// Gxh and Gu are fused): contraction is off and every fma is explicit, so
+// the 8-wide layout cannot shift them.
+// ---------------------------------------------------------------------------
+template <typename scalar_t, bool PER_TASK_AFFINE>
+__global__ void bn_dbwd_sums_vec_kernel(
+    const scalar_t* __restrict__ x, const scalar_t* __restrict__ u,
+    const scalar_t* __restrict__ gx, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ gamma,
+    const float* __restrict__ beta,
+    float* __restrict__ partials,  // [T, NSLICE, 5, C]
+    long M, int C, float slope, bool act, int R, int slices_per_block,
+    int nslice) {
+  const int c8n = C / 8;
+  const int c8 = threadIdx.x % c8n;
+  const int chain = threadIdx.x / c8n;  // (slice in block, rgroup)
+  const int sl = chain / R, rg = chain % R;
+  const int t = blockIdx.x;
+  const int slice = blockIdx.y * slices_per_block + sl;
+  const bool live = sl < slices_per_block && slice < nslice;
+  const int c0 = c8 * 8;
+  extern __shared__ float ls[];  // [chains][5][C]
+  if (live) {
+    float mu[8], r[8], g[8], b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const long tc = (long)t * C + c0 + j;
+      mu[j] = mean[tc]; r[j] = rstd[tc];
+      g[j] = PER_TASK_AFFINE ? gamma[tc] : gamma[c0 + j];
+      b[j] = PER_TASK_AFFINE ? beta[tc] : beta[c0 + j];
+    }
+    float s1[8] = {0}, s2[8] = {0}, G[8] = {0}, Gxh[8] = {0}, Gu[8] = {0};
+    const long base = (long)t * M * C + c0;
+    const long row0 = (long)slice * kRowsPerBlockD;
+    const long row_end = min(row0 + kRowsPerBlockD, M);
+    for (long m = row0 + rg; m < row_end; m += R) {
+      float xv[8], uv[8], gxv[8];
+      load8(x + base + m * C, xv);
+      load8(u + base + m * C, uv);
+      load8(gx + base + m * C, gxv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+#pragma clang fp contract(off)
+        const float xh = (xv[j] - mu[j]) * r[j];
+        float up = uv[j];
+        if (act) up = up * ((__builtin_fmaf(g[j], xh, b[j]) > 0.f) ? 1.f : slope);
+        const float gv = gxv[j];
+        const float upxh = up * xh;
+        s1[j] = s1[j] + up;
+        s2[j] = s2[j] + upxh;
+        G[j] = G[j] + gv;
+        Gxh[j] = __builtin_fmaf(gv, xh, Gxh[j]);
+        Gu[j] = __builtin_fmaf(gv, up, Gu[j]);
+      }
+    }
+    float* lc = ls + (long)chain * 5 * C + c0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      lc[0 * C + j] = s1[j];
+      lc[1 * C + j] = s2[j];
+      lc[2 * C + j] = G[j];
+      lc[3 * C + j] = Gxh[j];
+      lc[4 * C + j] = Gu[j];
+    }
+  }
+  __syncthreads();
+  if (live && rg == 0) {
+    // rgroup 0 + rgroup 1 + ... in this order, as the scalar kernel adds
+    float* pt = partials + (((long)t * nslice + slice) * 5) * C + c0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float v = ls[((long)chain * 5 + k) * C + c0 + j];
+        for (int rr = 1; rr < R; ++rr)
+          v += ls[((long)(chain + rr) * 5 + k) * C + c0 + j];
+        pt[k * C + j] = v;
+      }
+    }
+  }
+}
+
+namespace {
+
+// The two passes on x, u, gx [T, M, C].  vec_sums: the 8-channel sums kernel
+// where C allows it.  With d_gamma_t defined the reduce also finishes
+// d_gamma_t [T, C].  returns {d_u, d_x, sums[T,5,C]}
+std::vector<torch::Tensor> dbwd_run(const torch::Tensor& x,
+                                    const torch::Tensor& u,
+                                    const torch::Tensor& gx,
+                                    const torch::Tensor& mean,
+                                    const torch::Tensor& rstd,
+                                    const torch::Tensor& gamma,
+                                    const torch::Tensor& beta,
+                                    const torch::Tensor& ggam,
+                                    const torch::Tensor& gbet, double slope,
+                                    bool act, bool vec_sums,
+                                    torch::Tensor d_gamma_t) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous());
   const int T = (int)x.size(0);
   const long M = x.size(1);
   const int C = (int)x.size(2);
+  TORCH_CHECK(u.numel() == x.numel() && gx.numel() == x.numel());
   auto fopts = x.options().dtype(torch::kFloat32);
-  auto sums = torch::zeros({T, 5, C}, fopts);
+  auto sums = torch::empty({T, 5, C}, fopts);  // bn_reduce5 writes it whole
   auto d_u = torch::empty_like(x);
   auto d_x = torch::empty_like(x);
   auto gc = gamma.contiguous().to(torch::kFloat32);
@@ -204,11 +341,36 @@ std::vector<torch::Tensor> bn_act_dbwd(torch::Tensor x, torch::Tensor u,
   dim3 sums_grid(T, (unsigned)((M + kRowsPerBlockD - 1) / kRowsPerBlockD));
   const int lds_bytes = 5 * threads * (int)sizeof(float);
   const long total = (long)T * M * C;
+  // vector sums: a block owns spb 256-row slices, one (slice, rgroup) chain
+  // per thread; R = the scalar kernel's row groups per block
+  const int R = threads / cpad;
+  const int c8n = std::max(1, C / 8);
+  const int spb = std::max(1, std::min(kThreadsD / c8n / R, 16));
+  const int vblocks = ((int)sums_grid.y + spb - 1) / spb;
+  const int vlds_bytes = spb * R * 5 * C * (int)sizeof(float);
+  const bool vec = vec_sums && (C % 8 == 0) && C <= 512 && vblocks <= 65535;
+  TORCH_CHECK(!vec || spb * R * c8n <= kThreadsD);
+  const float Mf = (float)M;
+  const float invM = 1.0f / Mf;
+  const float* rstd_p = d_gamma_t.defined() ? rstd.data_ptr<float>() : nullptr;
+  float* dgam_p = d_gamma_t.defined() ? d_gamma_t.data_ptr<float>() : nullptr;
 
 #define LAUNCH_DB(ST, PT)                                                      \
   do {                                                                         \
     const int nblk = (int)sums_grid.y;                                         \
     auto partials = torch::empty({T, nblk, 5, C}, fopts);                      \
+    if (vec)                                                                   \
+      hipLaunchKernelGGL((bn_dbwd_sums_vec_kernel<ST, PT>),                    \
+                         dim3(T, vblocks), dim3(kThreadsD), vlds_bytes,        \
+                         stream.stream(),                                      \
+                         reinterpret_cast<const ST*>(x.data_ptr()),            \
+                         reinterpret_cast<const ST*>(uc.data_ptr()),           \
+                         reinterpret_cast<const ST*>(gxc.data_ptr()),          \
+                         mean.data_ptr<float>(), rstd.data_ptr<float>(),       \
+                         gc.data_ptr<float>(), bc.data_ptr<float>(),           \
+                         partials.data_ptr<float>(), M, C, (float)slope, act,  \
+                         R, spb, nblk);                                        \
+    else                                                                       \
     hipLaunchKernelGGL((bn_dbwd_sums_kernel<ST, PT>), sums_grid,               \
                        dim3(threads), lds_bytes, stream.stream(),              \
                        reinterpret_cast<const ST*>(x.data_ptr()),              \
@@ -221,7 +383,7 @@ std::vector<torch::Tensor> bn_act_dbwd(torch::Tensor x, torch::Tensor u,
     hipLaunchKernelGGL(bn_reduce5_kernel, dim3((T * C + 255) / 256),           \
                        dim3(256), 0, stream.stream(),                          \
                        partials.data_ptr<float>(), sums.data_ptr<float>(),     \
-                       T, nblk, C);                                            \
+                       T, nblk, C, rstd_p, dgam_p, Mf, invM);                  \
     hipLaunchKernelGGL((bn_dbwd_apply_kernel<ST, PT>),                         \
                        dim3(ew_grid(total, kThreadsD)), dim3(kThreadsD), 0,    \
                        stream.stream(),                                        \
@@ -245,4 +407,45 @@ std::vector<torch::Tensor> bn_act_dbwd(torch::Tensor x, torch::Tensor u,
   }
 #undef LAUNCH_DB
   return {d_u, d_x, sums};
+}
+
+}  // namespace
+
+// returns {d_u, d_x, sums[T,5,C]} — d_gamma_t is finished by the wrapper:
+//   d_gamma_t = rstd * (Gu_sum - s1m*G_sum... see hip_autograd (cheap [T,C]).
+std::vector<torch::Tensor> bn_act_dbwd(torch::Tensor x, torch::Tensor u,
+                                       torch::Tensor gx, torch::Tensor mean,
+                                       torch::Tensor rstd, torch::Tensor gamma,
+                                       torch::Tensor beta, torch::Tensor ggam,
+                                       torch::Tensor gbet, double slope,
+                                       bool act) {
+  return dbwd_run(x, u, gx, mean, rstd, gamma, beta, ggam, gbet, slope, act,
+                  /*vec_sums=*/false, torch::Tensor());
+}
+
+// The same two passes as one call for the autograd backward: absent
+// ggam / gbet ([T,C] fp32) read as zero, the sums pass runs 8 channels per
+// thread where C allows (bits unchanged), and the reduce finishes
+// d_gamma_t = rstd * M * (Gu - s1*G - s2*Gxh) with the bits of the tensor
+// formula it replaces.  returns {d_u, d_x, d_gamma_t [T,C], sums [T,5,C]}
+std::vector<torch::Tensor> bn_act_dbwd_full(
+    torch::Tensor x, torch::Tensor u, torch::Tensor gx, torch::Tensor mean,
+    torch::Tensor rstd, torch::Tensor gamma, torch::Tensor beta,
+    c10::optional<torch::Tensor> ggam, c10::optional<torch::Tensor> gbet,
+    double slope, bool act) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3);
+  const long T = x.size(0), C = x.size(2);
+  TORCH_CHECK(mean.numel() == T * C && rstd.numel() == T * C);
+  auto fopts = x.options().dtype(torch::kFloat32);
+  const bool has_gg = ggam.has_value() && ggam->defined();
+  const bool has_gb = gbet.has_value() && gbet->defined();
+  TORCH_CHECK((!has_gg || ggam->numel() == T * C) &&
+              (!has_gb || gbet->numel() == T * C));
+  torch::Tensor zero;
+  if (!has_gg || !has_gb) zero = torch::zeros({T, C}, fopts);
+  auto d_gamma_t = torch::empty({T, C}, fopts);
+  auto out = dbwd_run(x, u, gx, mean, rstd, gamma, beta,
+                      has_gg ? *ggam : zero, has_gb ? *gbet : zero, slope, act,
+                      /*vec_sums=*/true, d_gamma_t);
+  return {out[0], out[1], d_gamma_t, out[2]};
 }

@@ -143,6 +143,73 @@ __global__ void maxpool_bwd_vec_kernel(const scalar_t* __restrict__ dy,
   }
 }
 
+// gather through a saved mask: y(n,ho,wo,c) = x at the window's argmax.
+// The double-backward of the pool backward (and the pool forward with the
+// routing held fixed): values only move.  C % 8 == 0 (the fused BN+act+pool
+// op's own requirement).
+// one thread per (pooled position, 8-channel group); the position is decoded
+// once in 32 bits per thread-iteration (the launcher checks the extents)
+template <typename scalar_t>
+__global__ void maxpool_gather_vec_kernel(const scalar_t* __restrict__ x,
+                                          const unsigned char* __restrict__ mask,
+                                          scalar_t* __restrict__ y,
+                                          unsigned total, int H, int W, int C,
+                                          int Ho, int Wo) {
+  const unsigned c8n = C / 8;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += blockDim.x * gridDim.x) {
+    const unsigned c8 = i % c8n;
+    unsigned r = i / c8n;
+    const unsigned wo = r % Wo; r /= Wo;
+    const unsigned ho = r % Ho;
+    const unsigned n = r / Ho;
+    const long base = (((long)n * H + 2 * ho) * W + 2 * wo) * C + c8 * 8;
+    float v[4][8], out[8];
+    load8(&x[base], v[0]);
+    load8(&x[base + C], v[1]);
+    load8(&x[base + (long)W * C], v[2]);
+    load8(&x[base + (long)W * C + C], v[3]);
+    const long o = (long)i * 8;  // == ((n*Ho + ho)*Wo + wo)*C + c8*8
+    const unsigned long long mp = *(const unsigned long long*)&mask[o];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int a = (int)((mp >> (8 * j)) & 3);
+      out[j] = a == 0 ? v[0][j] : a == 1 ? v[1][j] : a == 2 ? v[2][j] : v[3][j];
+    }
+    store8(&y[o], out);
+  }
+}
+
+// x: [N, H, W, C], mask: [N, H/2, W/2, C] u8 -> [N, H/2, W/2, C]
+torch::Tensor maxpool2x2_gather(torch::Tensor x, torch::Tensor mask) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && mask.dim() == 4);
+  auto xc = x.contiguous();
+  auto mc = mask.contiguous();
+  const long N = x.size(0);
+  const int H = (int)x.size(1), W = (int)x.size(2), C = (int)x.size(3);
+  const int Ho = H / 2, Wo = W / 2;
+  TORCH_CHECK(mask.size(0) == N && mask.size(1) == Ho && mask.size(2) == Wo &&
+              mask.size(3) == C && mask.scalar_type() == torch::kUInt8);
+  auto y = torch::empty({N, Ho, Wo, C}, x.options());
+  TORCH_CHECK(C % 8 == 0, "maxpool2x2_gather needs C % 8 == 0");
+  const long total = N * (long)Ho * Wo * (C / 8);
+  TORCH_CHECK(total < (1L << 31), "maxpool2x2_gather: too many positions");
+  if (total == 0) return y;
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define LAUNCH_PG(st)                                                          \
+  hipLaunchKernelGGL((maxpool_gather_vec_kernel<st>),                          \
+                     dim3(ew_grid(total, 256)), dim3(256), 0, stream.stream(), \
+                     reinterpret_cast<const st*>(xc.data_ptr()),               \
+                     mc.data_ptr<unsigned char>(),                             \
+                     reinterpret_cast<st*>(y.data_ptr()), (unsigned)total, H,  \
+                     W, C, Ho, Wo)
+  if (x.scalar_type() == torch::kFloat32) LAUNCH_PG(float);
+  else if (x.scalar_type() == torch::kBFloat16) LAUNCH_PG(__hip_bfloat16);
+  else TORCH_CHECK(false, "maxpool2x2_gather: unsupported dtype");
+#undef LAUNCH_PG
+  return y;
+}
+
 // x: [N, H, W, C] contiguous (caller flattens T*NS -> N)
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor x) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());

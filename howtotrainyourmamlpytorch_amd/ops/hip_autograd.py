@@ -20,7 +20,11 @@ through the inner-loop support forward):
   kernel, whose backward is the forward kernel again);
 * the fused BN+act+pool op uses a single-pass fused backward when the
   backward itself is not being differentiated, and composes the
-  individual Functions under create_graph.
+  individual Functions under create_graph.  What runs under those
+  Functions' backwards is native: a gather kernel for the pool, one call
+  for the BN double-backward (``MAML355_BNPOOL_DBWD=0`` restores the
+  torch.gather glue, the tensor formula for d_gamma_t and the scalar sums
+  kernel; both give the same bits).
 
 fp32 activations (``--compute_dtype fp32``, ``--fp32_support_pass``): the
 stride-1 convs take the fconv.hip backend (exact fp32 MFMA, unrounded
@@ -50,6 +54,15 @@ def _ext():
     return e
 
 
+def _dbwd_glue_off() -> bool:
+    """The second-order BN / pool backward without ATen glue: the pool's
+    double-backward gather is a kernel, the BN double-backward is one native
+    call (vector sums, d_gamma_t finished in the reduce).  Every result
+    keeps its bits.  MAML355_BNPOOL_DBWD=0 restores the torch.gather glue,
+    the tensor formula for d_gamma_t and the scalar sums kernel (A/B)."""
+    return os.environ.get("MAML355_BNPOOL_DBWD", "1") != "0"
+
+
 # ---------------------------------------------------------------------------
 # fused BN + leaky-ReLU
 # ---------------------------------------------------------------------------
@@ -65,22 +78,34 @@ class _BNBwdFn(torch.autograd.Function):
             u, x3, mean, rstd, gamma.float(), beta.float(), slope, act)
         ctx.save_for_backward(x3, gamma, beta, u, mean, rstd)
         ctx.slope, ctx.act = slope, act
+        # absent grads stay None instead of zero-filled tensors
+        ctx.set_materialize_grads(False)
         return dx, dgamma_t, dbeta_t
 
     @staticmethod
     def backward(ctx, gx, ggam_t, gbet_t):
         x3, gamma, beta, u, mean, rstd = ctx.saved_tensors
         T, M, C = x3.shape
-        if ggam_t is None:
-            ggam_t = torch.zeros(T, C, device=x3.device, dtype=torch.float32)
-        if gbet_t is None:
-            gbet_t = torch.zeros(T, C, device=x3.device, dtype=torch.float32)
-        d_u, d_x, sums = _ext().bn_act_dbwd(
-            x3, u, gx.contiguous(), mean, rstd, gamma.float(), beta.float(),
-            ggam_t, gbet_t, ctx.slope, ctx.act)
-        # d_gamma_t = rstd * M * (Gu - s1*G - s2*Gxh)   (means over M)
-        s = sums / M   # [T,5,C] means: {0:s1, 1:s2, 2:G, 3:Gxh, 4:Gu}
-        d_gamma_t = rstd * M * (s[:, 4] - s[:, 0] * s[:, 2] - s[:, 1] * s[:, 3])
+        if gx is None:
+            gx = torch.zeros_like(x3)
+        if _dbwd_glue_off():
+            # one native call: absent ggam_t / gbet_t read as zero inside,
+            # d_gamma_t finished in the ordered reduce (same bits as the
+            # tensor formula below)
+            d_u, d_x, d_gamma_t, _ = _ext().bn_act_dbwd_full(
+                x3, u, gx.contiguous(), mean, rstd, gamma.float(),
+                beta.float(), ggam_t, gbet_t, ctx.slope, ctx.act)
+        else:
+            if ggam_t is None:
+                ggam_t = torch.zeros(T, C, device=x3.device, dtype=torch.float32)
+            if gbet_t is None:
+                gbet_t = torch.zeros(T, C, device=x3.device, dtype=torch.float32)
+            d_u, d_x, sums = _ext().bn_act_dbwd(
+                x3, u, gx.contiguous(), mean, rstd, gamma.float(), beta.float(),
+                ggam_t, gbet_t, ctx.slope, ctx.act)
+            # d_gamma_t = rstd * M * (Gu - s1*G - s2*Gxh)   (means over M)
+            s = sums / M   # [T,5,C] means: {0:s1, 1:s2, 2:G, 3:Gxh, 4:Gu}
+            d_gamma_t = rstd * M * (s[:, 4] - s[:, 0] * s[:, 2] - s[:, 1] * s[:, 3])
         per_task = gamma.dim() == 2
         d_gamma = d_gamma_t if per_task else d_gamma_t.sum(0)
         return (d_x, d_gamma.to(gamma.dtype), None, d_u, None, None, None, None)
@@ -121,7 +146,11 @@ class _BNActPoolFn(torch.autograd.Function):
     """Fused normalize+leakyReLU+2x2 maxpool FORWARD (one pass over the
     conv output instead of write+reread of the activation); the backward
     composes the existing differentiable pool-bwd and BN-bwd Functions, so
-    second-order behavior is identical to the unfused pair."""
+    second-order behavior is identical to the unfused pair.  (Running the
+    fused backward kernels under create_graph as one Function of their own
+    was tried: bitwise equal to the pair at the test shapes, but the
+    deterministic benchmark's outputs moved after three steps, so the pair
+    stays.)"""
 
     @staticmethod
     def forward(ctx, x5, gamma, beta, eps, slope, sums):
@@ -139,7 +168,8 @@ class _BNActPoolFn(torch.autograd.Function):
         Ho, Wo = H // 2, W // 2
         if torch.is_grad_enabled() or os.environ.get("MAML355_NO_BWDFUSE", "0") == "1":
             # create_graph (second-order inner loop): compose the
-            # differentiable Functions
+            # differentiable Functions (their backwards are native calls:
+            # a gather kernel and bn_act_dbwd_full)
             da = _PoolBwdFn.apply(dy.contiguous().view(T * NB, Ho, Wo, C),
                                   mask.view(T * NB, Ho, Wo, C), H, W)
             dx, dgamma_t, dbeta_t = _BNBwdFn.apply(
@@ -241,7 +271,10 @@ class _PoolBwdFn(torch.autograd.Function):
         (mask,) = ctx.saved_tensors
         # gather: d(dy) = ddx at the argmax positions == pool-forward of ddx
         # restricted to saved argmax — implemented by re-running fwd gather
-        g = _gather_by_mask(ddx.contiguous(), mask)
+        if mask.shape[-1] % 8 == 0 and _dbwd_glue_off():
+            g = _ext().maxpool2x2_gather(ddx.contiguous(), mask)
+        else:
+            g = _gather_by_mask(ddx.contiguous(), mask)
         return g, None, None, None
 
 

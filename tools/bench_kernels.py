@@ -9,6 +9,7 @@
     python tools/bench_kernels.py --conv-input      # pad copy / first-layer fwd A/B
     python tools/bench_kernels.py --fconv           # fp32 conv trio vs grouped ATen
     python tools/bench_kernels.py --fconv-model     # fp32 modes, whole-model A/B
+    python tools/bench_kernels.py --bn-pool-dbwd    # support BN+pool bwd / dbwd A/B
 
 Prints per-kernel time, effective TFLOP/s (conv) or TB/s (memory-bound),
 so optimization effort goes where the roofline says.
@@ -720,9 +721,76 @@ def main_fconv(with_model):
             bench_fconv_model("maml++_omniglot_20w5s", 32, mode)
 
 
+def bench_bn_pool_dbwd(T, NB, H, W, C, tag):
+    """Support-side BN+act+pool block under create_graph: the whole first
+    backward and the whole double-backward, native path against
+    MAML355_BNPOOL_DBWD=0 (torch.gather glue, tensor formula for d_gamma,
+    scalar sums kernel), interleaved.  The first backward is the same
+    composition in both; it is timed as the control.
+    Floor: the bytes the result needs at 6.3 TB/s — backward: x twice, the
+    pooled dy and mask twice, dx once; double-backward: x and gx twice, the
+    pooled dy and mask twice, d_x and the pooled d_dy once."""
+    import os
+    dev = torch.device("cuda")
+    env = "MAML355_BNPOOL_DBWD"
+    Ho, Wo = H // 2, W // 2
+    x = torch.randn(T, NB, H, W, C, device=dev).to(torch.bfloat16).requires_grad_(True)
+    gam = (torch.rand(T, C, device=dev) + 0.5).requires_grad_(True)
+    bet = torch.randn(T, C, device=dev).requires_grad_(True)
+    gy = torch.randn(T, NB, Ho, Wo, C, device=dev).to(torch.bfloat16).requires_grad_(True)
+    rx = torch.randn(T, NB, H, W, C, device=dev).to(torch.bfloat16)
+    rg, rb = torch.randn(T, C, device=dev), torch.randn(T, C, device=dev)
+    y, _, _ = ops.task_bn_act_pool(x, gam, bet, 1e-5, 0.01)
+
+    def first(flag):
+        def run():
+            os.environ[env] = flag
+            return torch.autograd.grad(y, (x, gam, bet), gy, create_graph=True,
+                                       retain_graph=True)
+        return run
+
+    def second(flag):
+        os.environ[env] = flag
+        outs = first(flag)()
+
+        def run():
+            os.environ[env] = flag
+            return torch.autograd.grad(outs, (x, gy, gam), (rx, rg, rb),
+                                       retain_graph=True)
+        return run
+
+    try:
+        same = all(torch.equal(a, b) for a, b in
+                   zip(first("1")() + second("1")(), first("0")() + second("0")()))
+        b0, b1 = _median_rounds([first("0"), first("1")], rounds=3, reps=5, warmup=2)
+        d0, d1 = _median_rounds([second("0"), second("1")], rounds=3, reps=5, warmup=2)
+    finally:
+        os.environ.pop(env, None)
+    n = 2.0 * T * NB * H * W * C            # one full-resolution bf16 tensor
+    p = 3.0 * T * NB * Ho * Wo * C          # pooled bf16 tensor + its mask
+    fb, fd = (3 * n + 2 * p) / 6.3e12, (6 * n + 2 * p + p * 2 / 3) / 6.3e12
+    print(f"[bn-pool-dbwd {tag}] T{T} NB{NB} {H}x{W} C{C} bits_equal={same} | "
+          f"bwd composed {b0*1e6:7.1f}us native {b1*1e6:7.1f}us x{b0/b1:4.2f} "
+          f"floor {fb*1e6:6.1f}us ratio {b1/fb:4.1f} | dbwd composed "
+          f"{d0*1e6:7.1f}us native {d1*1e6:7.1f}us x{d0/d1:4.2f} "
+          f"floor {fd*1e6:6.1f}us ratio {d1/fd:4.1f}", flush=True)
+
+
+def main_bn_pool_dbwd():
+    # the four support stages: mini-imagenet 5w1s at 128 tasks (5 images),
+    # omniglot 20w5s at 32 tasks (100 images)
+    for hw in (84, 42, 21, 10):
+        bench_bn_pool_dbwd(128, 5, hw, hw, 48, f"mi-{hw}")
+    for hw in (28, 14, 7, 3):
+        bench_bn_pool_dbwd(32, 100, hw, hw, 64, f"om-{hw}")
+
+
 def main():
     assert torch.cuda.is_available()
     print(torch.cuda.get_device_name(0))
+    if "--bn-pool-dbwd" in sys.argv:
+        main_bn_pool_dbwd()
+        return
     if "--fconv" in sys.argv or "--fconv-model" in sys.argv:
         main_fconv("--fconv-model" in sys.argv)
         return
