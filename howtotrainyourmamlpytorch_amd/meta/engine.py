@@ -161,6 +161,12 @@ class MAMLFewShotClassifier(nn.Module):
                       and epoch < self.args.multi_step_loss_num_epochs)
         importance = self.get_per_step_loss_importance_vector()
 
+        # the images are the same at every inner step: put them into the
+        # first layer's kernel layouts once (None where that layer takes
+        # them as they are)
+        xs_prep = self.classifier.prepare_input(xs)
+        xt_prep = self.classifier.prepare_input(xt)
+
         arena = self.classifier.init_arena(T)
         per_step_target_loss: List[torch.Tensor] = []
         final_logits = None
@@ -168,7 +174,8 @@ class MAMLFewShotClassifier(nn.Module):
         for step in range(num_steps):
             support_logits = self.classifier(xs, num_step=step, arena=arena,
                                              training=True,
-                                             backup_running_statistics=(step == 0))
+                                             backup_running_statistics=(step == 0),
+                                             prepared=xs_prep)
             support_loss = ops.softmax_cross_entropy(support_logits, ys)  # [T]
             # first-order / eval: the support graph is not traversed again,
             # so its activation buffers are freed here (retain only under
@@ -179,7 +186,8 @@ class MAMLFewShotClassifier(nn.Module):
             arena = ops.lslr_update(arena, grad, lr_vec)
 
             if msl_active:
-                tl = self.classifier(xt, num_step=step, arena=arena, training=True)
+                tl = self.classifier(xt, num_step=step, arena=arena, training=True,
+                                     prepared=xt_prep)
                 per_step_target_loss.append(ops.softmax_cross_entropy(tl, yt))
                 if step == num_steps - 1:
                     final_logits = tl
@@ -188,7 +196,7 @@ class MAMLFewShotClassifier(nn.Module):
                 # training — skip graph construction at eval
                 with torch.set_grad_enabled(training_phase):
                     final_logits = self.classifier(xt, num_step=step, arena=arena,
-                                                   training=True)
+                                                   training=True, prepared=xt_prep)
                     per_step_target_loss.append(
                         ops.softmax_cross_entropy(final_logits, yt))
 

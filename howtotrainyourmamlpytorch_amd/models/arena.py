@@ -19,6 +19,7 @@ Layers see the arena through zero-copy views produced by :meth:`views`.
 
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Dict, List, Sequence, Tuple
 
@@ -32,6 +33,56 @@ class ParamSpec:
     offset: int          # element offset into the flat arena
     numel: int
     slot: int            # LSLR slot id (one learnable per-step LR per spec)
+
+
+class _ArenaViewsFn(torch.autograd.Function):
+    """arena [T, P] -> the per-parameter views (zero-copy, as plain slicing
+    gives them).  Backward: the view gradients written side by side into one
+    [T, P] tensor by ``_ArenaScatterFn`` — one launch.  A view without a
+    gradient stays absent (a zero range in the kernel), never a tensor."""
+
+    @staticmethod
+    def forward(ctx, pa, arena):
+        ctx.pa = pa
+        ctx.set_materialize_grads(False)
+        return tuple(pa._slices(arena))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if all(g is None for g in grads):
+            return None, None
+        return None, _ArenaScatterFn.apply(ctx.pa, *grads)
+
+
+class _ArenaScatterFn(torch.autograd.Function):
+    """Per-parameter gradients [T, *shape] (None = absent) -> [T, P].
+    Linear, and the adjoint of slicing: its backward hands out the slices of
+    the incoming [T, P] gradient (views, no kernel), through
+    ``_ArenaViewsFn`` again where that gradient is itself differentiated —
+    the two Functions are each other's backward, at every order."""
+
+    @staticmethod
+    def forward(ctx, pa, *grads):
+        from .. import ops
+        ctx.pa = pa
+        ctx.present = [g is not None for g in grads]
+        ctx.set_materialize_grads(False)
+        slots = [i for i, g in enumerate(grads) if g is not None]
+        T = grads[slots[0]].shape[0]
+        return ops.hip_ext().arena_scatter(
+            [grads[i] for i in slots], slots,
+            [s.offset for s in pa.specs], [s.numel for s in pa.specs],
+            T, pa.numel)
+
+    @staticmethod
+    def backward(ctx, gout):
+        if gout is None:
+            return (None,) * (1 + len(ctx.present))
+        pa = ctx.pa
+        vs = (_ArenaViewsFn.apply(pa, gout) if pa._native_grad(gout)
+              else pa._slices(gout))
+        return (None,) + tuple(v if p else None
+                               for v, p in zip(vs, ctx.present))
 
 
 class ParamArena:
@@ -72,20 +123,53 @@ class ParamArena:
             flat[s.offset:s.offset + s.numel] = named[s.name].detach().reshape(-1).float()
         return flat
 
+    def _slices(self, arena: torch.Tensor) -> List[torch.Tensor]:
+        """[T, P] -> the per-parameter views [T, *shape], in spec order."""
+        T = arena.shape[0]
+        return [arena[:, s.offset:s.offset + s.numel].view(T, *s.shape)
+                for s in self.specs]
+
+    def _native_grad(self, arena: torch.Tensor) -> bool:
+        """Whether views() of this [T, P] arena goes through the Function
+        pair with the one-launch gradient (``arena_scatter``): an fp32 arena
+        that requires grad, on the GPU, with the extension loaded, at most
+        32 parameters (the kernel's table), and MAML355_ARENA_SCATTER=1.
+        Opt-in for now: every gradient it was compared on has the bits of
+        autograd's own slice backward, but the flagship's deterministic
+        output dump moves from the second training step on (DESIGN.md);
+        unset or 0 is the slice backward."""
+        if not (arena.is_cuda and arena.requires_grad
+                and arena.dtype == torch.float32
+                and len(self.specs) <= 32
+                and os.environ.get("MAML355_ARENA_SCATTER", "0") == "1"):
+            return False
+        from .. import ops
+        return ops.hip_ext() is not None
+
     def views(self, arena: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Zero-copy per-parameter views.
 
         arena [P]   -> name -> [*shape]
         arena [T,P] -> name -> [T, *shape]
+
+        With MAML355_ARENA_SCATTER=1 a ``[T, P]`` arena that requires grad
+        on the GPU gets its views from ``_ArenaViewsFn``: the same views, whose gradient is one
+        ``arena_scatter`` launch instead of a zero-filled ``[T, P]`` tensor
+        per view and their sum.  The views of such an arena must not be
+        written in place (nothing does: fast weights are replaced by
+        ``lslr_update``, never updated); autograd refuses such a write.
         """
         out: Dict[str, torch.Tensor] = {}
         if arena.dim() == 1:
             for s in self.specs:
                 out[s.name] = arena[s.offset:s.offset + s.numel].view(*s.shape)
         elif arena.dim() == 2:
-            T = arena.shape[0]
-            for s in self.specs:
-                out[s.name] = arena[:, s.offset:s.offset + s.numel].view(T, *s.shape)
+            if self._native_grad(arena):
+                vs = _ArenaViewsFn.apply(self, arena)
+            else:
+                vs = self._slices(arena)
+            for s, v in zip(self.specs, vs):
+                out[s.name] = v
         else:
             raise ValueError("arena must be [P] or [T, P], got %s" % (arena.shape,))
         return out

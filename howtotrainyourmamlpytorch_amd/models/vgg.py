@@ -202,9 +202,19 @@ class TaskBatchedVGG(nn.Module):
                                  self._slot_bounds)
 
     # ------------------------------------------------------------------
+    def prepare_input(self, x: torch.Tensor):
+        """The images of one iteration in the form the first layer's kernels
+        read, made once and passed to every ``forward`` over the same images
+        (``prepared=``); None where the first layer takes the images as they
+        are."""
+        return ops.prepare_conv_input(x, self.num_filters,
+                                      stride=1 if self.max_pooling else 2)
+
     def forward(self, x: torch.Tensor, num_step: int, arena: torch.Tensor,
-                training: bool = True, backup_running_statistics: bool = False) -> torch.Tensor:
+                training: bool = True, backup_running_statistics: bool = False,
+                prepared=None) -> torch.Tensor:
         """x: [T, NS, C, H, W] images; arena: [T, P] fast weights.
+        ``prepared``: ``prepare_input(x)`` of the same x, or None.
         Returns logits [T, NS, ways].
 
         Running BN statistics are updated on every call (the reference
@@ -216,7 +226,10 @@ class TaskBatchedVGG(nn.Module):
         if backup_running_statistics:
             self._backup_stats()
 
-        out = x.permute(0, 1, 3, 4, 2)  # NHWC
+        if prepared is not None:
+            out, xpad = prepared.nhwc, prepared.xpad
+        else:
+            out, xpad = x.permute(0, 1, 3, 4, 2), None  # NHWC
         stride = 1 if self.max_pooling else 2
         pad = 1 if self.conv_padding else 0
         for i in range(self.num_stages):
@@ -234,9 +247,12 @@ class TaskBatchedVGG(nn.Module):
             bn_sums = None
             if want_stats:
                 out, bn_sums = ops.task_conv3x3(out, w_i, b_i, stride=stride,
-                                                padding=pad, return_stats=True)
+                                                padding=pad, return_stats=True,
+                                                xpad=xpad)
             else:
-                out = ops.task_conv3x3(out, w_i, b_i, stride=stride, padding=pad)
+                out = ops.task_conv3x3(out, w_i, b_i, stride=stride, padding=pad,
+                                       xpad=xpad)
+            xpad = None  # the first layer's only
             if self.norm_layer_type == "batch_norm":
                 gamma, beta = self._bn_affine(i, num_step, v)
                 stat_count = out[0].numel() // out.shape[-1]

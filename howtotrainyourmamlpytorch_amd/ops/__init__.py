@@ -77,10 +77,23 @@ def _want_hip(x: torch.Tensor) -> bool:
 # public ops — HIP autograd wrappers are registered here as they land
 # ---------------------------------------------------------------------------
 
-def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
+def prepare_conv_input(x, num_filters, stride=1):
+    """The first conv layer's input prepared once for every pass that reads
+    the same images: x [T, NS, C, H, W] -> (nhwc, xpad), or None where the
+    layer does not run on the kernels that read them (CPU, kernels disabled,
+    fp32, stride 2, C not in {1, 3}, MAML355_INPUT_PREP=0)."""
+    if x.is_cuda and _want_hip(x):
+        from . import hip_autograd
+        return hip_autograd.prepare_conv_input(x, num_filters, stride)
+    return None
+
+
+def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False,
+                 xpad=None):
     if _want_hip(x):
         from . import hip_autograd
-        return hip_autograd.task_conv3x3(x, w, b, stride, padding, return_stats)
+        return hip_autograd.task_conv3x3(x, w, b, stride, padding, return_stats,
+                                         xpad)
     # kernels disabled with bf16 activations: the fp32 arena views are cast
     # like the grouped-ATen fallback does (no-op for the fp32 CPU path)
     y = ref.task_conv3x3(x, w.to(x.dtype),

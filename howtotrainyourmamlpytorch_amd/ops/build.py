@@ -21,6 +21,7 @@ SOURCES = [
     os.path.join(HIP_DIR, "pool.hip"),
     os.path.join(HIP_DIR, "softmax_ce.hip"),
     os.path.join(HIP_DIR, "lslr.hip"),
+    os.path.join(HIP_DIR, "arena.hip"),
     os.path.join(HIP_DIR, "tconv.hip"),
     os.path.join(HIP_DIR, "wgrad_nt.hip"),
     os.path.join(HIP_DIR, "bn_dbwd.hip"),

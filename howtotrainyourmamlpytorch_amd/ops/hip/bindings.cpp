@@ -52,6 +52,11 @@ std::vector<torch::Tensor> ln_act_dbwd(torch::Tensor x, torch::Tensor dy,
 torch::Tensor lslr_fwd(torch::Tensor arena, torch::Tensor grad, torch::Tensor lr_vec);
 std::vector<torch::Tensor> lslr_bwd(torch::Tensor gout, torch::Tensor grad,
                                     torch::Tensor lr_vec);
+// arena.hip
+torch::Tensor arena_scatter(std::vector<torch::Tensor> grads,
+                            std::vector<int64_t> slots,
+                            std::vector<int64_t> offsets,
+                            std::vector<int64_t> numels, int64_t T, int64_t P);
 // tconv.hip
 torch::Tensor tconv_repack(torch::Tensor w, bool dgrad);
 std::vector<torch::Tensor> tconv_mm(torch::Tensor x, torch::Tensor wp,
@@ -64,7 +69,10 @@ std::vector<torch::Tensor> tconv_wgrad_v2(torch::Tensor dy, torch::Tensor x,
                                           long pad, bool with_bias);
 // wgrad_nt.hip
 std::vector<torch::Tensor> tconv_wgrad_v3(torch::Tensor dy, torch::Tensor x,
-                                          long pad, bool with_bias);
+                                          long pad, bool with_bias,
+                                          c10::optional<torch::Tensor> xpad);
+std::vector<torch::Tensor> conv_input_prep(torch::Tensor x);
+torch::Tensor tconv_chpad8(torch::Tensor x);
 // dconv.hip
 torch::Tensor dconv_fwd(torch::Tensor x, torch::Tensor w,
                         c10::optional<torch::Tensor> bias, long pad,
@@ -138,7 +146,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tconv_wgrad_v2", &tconv_wgrad_v2,
         "async-pipelined wgrad via k-contiguous operand transposes (v2)");
   m.def("tconv_wgrad_v3", &tconv_wgrad_v3,
-        "transpose-free wgrad: operands staged as stored, transposing LDS reads (v3)");
+        "transpose-free wgrad: operands staged as stored, transposing LDS reads (v3)",
+        py::arg("dy"), py::arg("x"), py::arg("pad"), py::arg("with_bias"),
+        py::arg("xpad") = py::none());
+  m.def("tconv_chpad8", &tconv_chpad8,
+        "wgrad v3's first-layer pad pass: C < 8 channels -> 8, zero-filled");
+  m.def("conv_input_prep", &conv_input_prep,
+        "first-layer images -> NHWC and 8-channel zero-padded NHWC, one pass");
+  m.def("arena_scatter", &arena_scatter,
+        "per-parameter gradients -> the [T, P] arena gradient, one launch");
   m.def("dconv_fwd", &dconv_fwd, "direct small-C conv fwd (VALU)");
   m.def("dconv_wgrad", &dconv_wgrad, "direct small-C conv wgrad (VALU)");
   m.def("lin_fwd", &lin_fwd, "task-batched linear head fwd");

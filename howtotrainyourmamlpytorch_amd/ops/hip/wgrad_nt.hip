@@ -61,6 +61,80 @@ __global__ void nt_chpad8_kernel(const bf16* __restrict__ x,
   }
 }
 
+// x [T, NB, H, W, C] bf16, C < 8 -> [T, NB, H, W, 8]: the pad pass of
+// tconv_wgrad_v3 on its own (what a pre-padded xpad must equal)
+torch::Tensor tconv_chpad8(torch::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 5 && x.size(4) < 8 &&
+              x.scalar_type() == torch::kBFloat16);
+  auto xc = x.contiguous();
+  const long M = x.size(0) * x.size(1) * x.size(2) * x.size(3);
+  auto xp = torch::empty({x.size(0), x.size(1), x.size(2), x.size(3), 8},
+                         x.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(nt_chpad8_kernel,
+                     dim3((unsigned)std::min<long>((M + 255) / 256, 65536)),
+                     dim3(256), 0, stream.stream(),
+                     reinterpret_cast<const bf16*>(xc.data_ptr()),
+                     reinterpret_cast<bf16*>(xp.data_ptr()), M,
+                     (int)x.size(4));
+  return xp;
+}
+
+// The first layer's input, prepared once for every pass that reads it:
+// images x [N, C, HW] (C < 8) in one pass -> nhwc [N * HW, C], what dconv_fwd
+// reads, and xp [N * HW, 8], the tensor nt_chpad8_kernel makes of nhwc.
+// nhwc may be null (C == 1: the images already are their own NHWC form).
+template <int C>
+__global__ void nt_input_prep_kernel(const bf16* __restrict__ x,
+                                     bf16* __restrict__ nhwc,
+                                     bf16* __restrict__ xp, long M, long HW) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < M;
+       i += grid_stride()) {
+    const long n = i / HW;
+    const short* s = (const short*)x + n * C * HW + (i - n * HW);
+    bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < C; ++j) v[j] = s[j * HW];
+    if (nhwc != nullptr) {
+#pragma unroll
+      for (int j = 0; j < C; ++j) ((short*)nhwc)[i * C + j] = v[j];
+    }
+    *(bf16x8*)((short*)xp + i * 8) = v;
+  }
+}
+
+// x [T, NS, C, H, W] bf16, C in {1, 3} -> {nhwc [T, NS, H, W, C],
+// xpad [T, NS, H, W, 8]}.  For C == 1 nhwc is a view of x.
+std::vector<torch::Tensor> conv_input_prep(torch::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 5 &&
+              x.scalar_type() == torch::kBFloat16);
+  const long T = x.size(0), NS = x.size(1), C = x.size(2), H = x.size(3),
+             W = x.size(4);
+  TORCH_CHECK(C == 1 || C == 3, "conv_input_prep needs C in {1, 3}");
+  auto xc = x.contiguous();
+  const long HW = H * W, M = T * NS * HW;
+  TORCH_CHECK(M >= 1, "conv_input_prep: empty input");
+  auto xp = torch::empty({T, NS, H, W, 8}, x.options());
+  auto nhwc = C == 1 ? xc.view({T, NS, H, W, 1})
+                     : torch::empty({T, NS, H, W, C}, x.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const dim3 grid((unsigned)std::min<long>((M + 255) / 256, 65536));
+  if (C == 1) {
+    hipLaunchKernelGGL(nt_input_prep_kernel<1>, grid, dim3(256), 0,
+                       stream.stream(),
+                       reinterpret_cast<const bf16*>(xc.data_ptr()),
+                       (bf16*)nullptr, reinterpret_cast<bf16*>(xp.data_ptr()),
+                       M, HW);
+  } else {
+    hipLaunchKernelGGL(nt_input_prep_kernel<3>, grid, dim3(256), 0,
+                       stream.stream(),
+                       reinterpret_cast<const bf16*>(xc.data_ptr()),
+                       reinterpret_cast<bf16*>(nhwc.data_ptr()),
+                       reinterpret_cast<bf16*>(xp.data_ptr()), M, HW);
+  }
+  return {nhwc, xp};
+}
+
 DEVINL bf16x4v lds_read_tr(const short* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) bf16x4v*)p);
@@ -257,8 +331,12 @@ void tconv_wgrad_nt_kernel(const bf16* __restrict__ dY,
 // dy [T, NB, Ho, Wo, F] bf16 ; x [T, NB, H, W, C] bf16
 // -> {dw [T, F, C, 3, 3] fp32, db [T, F] fp32}; same contract as
 // tconv_wgrad_v2.  Needs F % 8 == 0, F <= 64 and C % 8 == 0 or C in {1, 3}.
+// xpad, for C in {1, 3} only: x already zero-padded to 8 channels
+// ([T, NB, H, W, 8], what conv_input_prep returns), so the pad pass is
+// skipped.
 std::vector<torch::Tensor> tconv_wgrad_v3(torch::Tensor dy, torch::Tensor x,
-                                          long pad, bool with_bias) {
+                                          long pad, bool with_bias,
+                                          c10::optional<torch::Tensor> xpad) {
   TORCH_CHECK(dy.is_cuda() && x.is_cuda());
   TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 &&
               x.scalar_type() == torch::kBFloat16);
@@ -279,17 +357,21 @@ std::vector<torch::Tensor> tconv_wgrad_v3(torch::Tensor dy, torch::Tensor x,
 
   // first layer: pad the channels to one 16-byte chunk
   int Cp = C;
-  if (C % 8 != 0) {
+  const bool have_xpad = xpad.has_value() && xpad->defined();
+  TORCH_CHECK(!have_xpad || C % 8 != 0,
+              "wgrad_v3: a pre-padded x is for C in {1, 3} only");
+  if (have_xpad) {
+    TORCH_CHECK(xpad->is_cuda() && xpad->scalar_type() == torch::kBFloat16 &&
+                    xpad->is_contiguous() && xpad->dim() == 5 &&
+                    xpad->size(0) == T && xpad->size(1) == NB &&
+                    xpad->size(2) == H && xpad->size(3) == W &&
+                    xpad->size(4) == 8 && xpad->device() == x.device(),
+                "wgrad_v3: xpad must be contiguous bf16 [T, NB, H, W, 8]");
     Cp = 8;
-    const long M = (long)T * NB * H * W;
-    auto xp = torch::empty({T, NB, H, W, 8}, x.options());
-    hipLaunchKernelGGL(nt_chpad8_kernel,
-                       dim3((unsigned)std::min<long>((M + 255) / 256, 65536)),
-                       dim3(256), 0,
-                       stream.stream(),
-                       reinterpret_cast<const bf16*>(xc.data_ptr()),
-                       reinterpret_cast<bf16*>(xp.data_ptr()), M, C);
-    xc = xp;
+    xc = *xpad;
+  } else if (C % 8 != 0) {
+    Cp = 8;
+    xc = tconv_chpad8(xc);
   }
   // Deterministic mode keeps, bit for bit, the sums of the v2 / v1 routing
   // it replaces (deterministic results do not move with the kernel

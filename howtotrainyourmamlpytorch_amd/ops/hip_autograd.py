@@ -413,6 +413,10 @@ def lslr_update(arena, grad, lr_vec):
 #   dgrad(dy, w, pad, H, W) -> dx     (H, W explicit: under stride 2 two
 #                                      input sizes share one Ho)
 #   wgrad(dy, x, pad, with_bias) -> (dw, db)
+# The first layer's images can come with their 8-channel padded copy (xpad,
+# see prepare_conv_input): it rides on the ctx of the two Functions whose x
+# is the image, down to the backend's wgrad(dy, x, pad, with_bias, xpad).
+# _ConvDgradFn's wgrad has a gradient for its x operand, never the image.
 # ---------------------------------------------------------------------------
 _ConvBackend = collections.namedtuple("_ConvBackend", "fwd dgrad wgrad")
 
@@ -423,8 +427,8 @@ class _ConvFwdFn(torch.autograd.Function):
     the other backends return no sums (None)."""
 
     @staticmethod
-    def forward(ctx, be, x, w, b, pad, want_stats):
-        ctx.save_for_backward(x, w)
+    def forward(ctx, be, x, w, b, pad, want_stats, xpad=None):
+        ctx.save_for_backward(x, w, xpad)
         ctx.be, ctx.pad = be, pad
         ctx.has_bias = b is not None
         y, sums = be.fwd(x, w, b, pad, want_stats)
@@ -434,7 +438,7 @@ class _ConvFwdFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dsums):
-        x, w = ctx.saved_tensors
+        x, w, xpad = ctx.saved_tensors
         dy = dy.contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[1]:
@@ -442,16 +446,17 @@ class _ConvFwdFn(torch.autograd.Function):
                                     x.shape[2], x.shape[3])
         if ctx.needs_input_grad[2]:
             want_bias = ctx.has_bias and ctx.needs_input_grad[3]
-            dw, db = _ConvWgradFn.apply(ctx.be, dy, x, ctx.pad, want_bias)
+            dw, db = _ConvWgradFn.apply(ctx.be, dy, x, ctx.pad, want_bias,
+                                        xpad)
             if not want_bias:
                 db = None
         elif ctx.has_bias and ctx.needs_input_grad[3]:
             db = dy.float().sum(dim=(1, 2, 3))
-        return None, dx, dw, db, None, None
+        return None, dx, dw, db, None, None, None
 
 
-def _conv_fwd(be, x, w, b, pad):
-    return _ConvFwdFn.apply(be, x, w, b, pad, False)[0]
+def _conv_fwd(be, x, w, b, pad, xpad=None):
+    return _ConvFwdFn.apply(be, x, w, b, pad, False, xpad)[0]
 
 
 class _ConvDgradFn(torch.autograd.Function):
@@ -481,19 +486,23 @@ class _ConvWgradFn(torch.autograd.Function):
     reduction rides along instead of a separate big ATen sum."""
 
     @staticmethod
-    def forward(ctx, be, dy, x, pad, with_bias):
-        ctx.save_for_backward(dy, x)
+    def forward(ctx, be, dy, x, pad, with_bias, xpad=None):
+        ctx.save_for_backward(dy, x, xpad)
         ctx.be, ctx.pad = be, pad
-        dw, db = be.wgrad(dy, x, pad, with_bias)
+        if xpad is None:
+            dw, db = be.wgrad(dy, x, pad, with_bias)
+        else:
+            dw, db = be.wgrad(dy, x, pad, with_bias, xpad)
         return dw, db
 
     @staticmethod
     def backward(ctx, gw, gdb):
-        dy, x = ctx.saved_tensors
+        dy, x, xpad = ctx.saved_tensors
         d_dy = d_x = None
         if ctx.needs_input_grad[1]:
             if gw is not None:
-                d_dy = _conv_fwd(ctx.be, x, gw.contiguous(), None, ctx.pad)
+                d_dy = _conv_fwd(ctx.be, x, gw.contiguous(), None, ctx.pad,
+                                 xpad)
             if gdb is not None:
                 T, F = gdb.shape
                 add = gdb.view(T, 1, 1, 1, F).to(dy.dtype)
@@ -501,7 +510,7 @@ class _ConvWgradFn(torch.autograd.Function):
         if ctx.needs_input_grad[2] and gw is not None:
             d_x = _ConvDgradFn.apply(ctx.be, dy, gw.contiguous(), ctx.pad,
                                      x.shape[2], x.shape[3])
-        return None, d_dy, d_x, None, None
+        return None, d_dy, d_x, None, None, None
 
 
 # ---------------------------------------------------------------------------
@@ -561,7 +570,7 @@ def _tconv_dgrad(dy, w, pad, H, W):
     return _ext().tconv_mm(dy, wp, None, 2 - pad, H, W, False)[0]
 
 
-def _tconv_wgrad(dy, x, pad, with_bias):
+def _tconv_wgrad(dy, x, pad, with_bias, xpad=None):
     # The direct VALU wgrad (dconv_wgrad) measured 2.3x SLOWER than v2 at
     # the conv0 shape (serial position walk per wave) — opt-in only.
     if (x.shape[4] <= 8 and dy.shape[4] <= 64
@@ -570,7 +579,8 @@ def _tconv_wgrad(dy, x, pad, with_bias):
     if _wgrad_v3_ok(x.shape[4], dy.shape[4]):
         # v3: both operands staged as stored, the transpose moved into
         # the LDS read — none of v2's operand copies
-        return _ext().tconv_wgrad_v3(dy, x, pad, with_bias)
+        # (xpad: the first layer's x already padded to 8 channels)
+        return _ext().tconv_wgrad_v3(dy, x, pad, with_bias, xpad)
     if (dy.shape[4] <= 64
             and dy.shape[1] * dy.shape[2] * dy.shape[3] >= 30000
             and os.environ.get("MAML355_WGRAD_V2", "1") != "0"):
@@ -583,6 +593,31 @@ def _tconv_wgrad(dy, x, pad, with_bias):
 
 
 _TCONV = _ConvBackend(_tconv_fwd, _tconv_dgrad, _tconv_wgrad)
+
+
+def _input_prep_on() -> bool:
+    """MAML355_INPUT_PREP=0 restores the NHWC copy at every classifier call
+    and the channel pad at every first-layer wgrad call (A/B; same bits)."""
+    return os.environ.get("MAML355_INPUT_PREP", "1") != "0"
+
+
+class PreparedInput(collections.namedtuple("PreparedInput", "nhwc xpad")):
+    """The first conv layer's input as its kernels read it: ``nhwc``
+    [T, NS, H, W, C] for dconv_fwd, ``xpad`` [T, NS, H, W, 8] (zero-padded
+    channels) for tconv_wgrad_v3.  Both bf16, without a gradient."""
+
+
+def prepare_conv_input(x, num_filters, stride=1):
+    """x [T, NS, C, H, W] images -> PreparedInput in one pass, or None where
+    the first layer does not run on dconv_fwd + tconv_wgrad_v3 (then the
+    layer prepares its input itself, as before)."""
+    C = x.shape[2]
+    if not (x.dtype == torch.bfloat16 and not x.requires_grad and stride == 1
+            and C in (1, 3) and x.numel() > 0 and _input_prep_on()
+            and _dconv_ok(C, num_filters) and _wgrad_v3_ok(C, num_filters)
+            and os.environ.get("MAML355_DCONV_WGRAD", "0") != "1"):
+        return None
+    return PreparedInput(*_ext().conv_input_prep(x))
 
 
 # ---------------------------------------------------------------------------
@@ -650,8 +685,11 @@ def _warn_fallback(reason: str) -> None:
             stacklevel=3)
 
 
-def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
+def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False,
+                 xpad=None):
     # w is task-batched [T, F, C, 3, 3]: dim 1 = out-channels, dim 2 = in
+    # xpad: PreparedInput.xpad of x, only ever given for the bf16 stride-1
+    # first layer (prepare_conv_input returns None for everything else)
     if (x.dtype == torch.float32 and stride == 1 and padding in (0, 1)
             and w.shape[1] <= 64 and w.shape[2] <= 64 and _fconv_on()):
         # fp32 activations: the fp32 MFMA trio, weights and bias unrounded.
@@ -698,7 +736,7 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False):
         w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 8 - C))
     y, sums = _ConvFwdFn.apply(_TCONV, x.contiguous(), w.contiguous(),
                                b.contiguous() if b is not None else None,
-                               padding, return_stats)
+                               padding, return_stats, xpad)
     return (y, sums) if return_stats else y
 
 
