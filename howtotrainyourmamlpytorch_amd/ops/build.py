@@ -32,6 +32,7 @@ SOURCES = [
     os.path.join(HIP_DIR, "gavgpool.hip"),
     os.path.join(HIP_DIR, "layernorm.hip"),
     os.path.join(HIP_DIR, "fconv.hip"),
+    os.path.join(HIP_DIR, "wconv.hip"),
 ]
 
 

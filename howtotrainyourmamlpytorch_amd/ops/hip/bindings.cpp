@@ -105,6 +105,15 @@ torch::Tensor fconv_mm(torch::Tensor x, torch::Tensor wp,
                        long Ho, long Wo);
 std::vector<torch::Tensor> fconv_wgrad(torch::Tensor dy, torch::Tensor x,
                                        long pad, bool with_bias);
+// wconv.hip
+torch::Tensor wconv_repack(torch::Tensor w, bool flip);
+torch::Tensor wconv_mm(torch::Tensor x, torch::Tensor wp,
+                       c10::optional<torch::Tensor> bias, long pad,
+                       long Ho, long Wo);
+std::vector<torch::Tensor> wconv_wgrad(torch::Tensor dy, torch::Tensor x,
+                                       long pad, bool with_bias);
+std::vector<long> wconv_wgrad_plan(long T, long NB, long Ho, long Wo, long C,
+                                   long F);
 // gavgpool.hip
 torch::Tensor gavgpool_fwd(torch::Tensor x);
 torch::Tensor gavgpool_bwd(torch::Tensor dy, long H, long W);
@@ -172,6 +181,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fconv_mm", &fconv_mm, "task-batched fp32 MFMA 3x3 conv fwd/dgrad");
   m.def("fconv_wgrad", &fconv_wgrad,
         "task-batched fp32 MFMA 3x3 conv weight/bias grads (ordered split-K)");
+  m.def("wconv_repack", &wconv_repack,
+        "repack conv weights for the wide-channel bf16 MFMA kernel (fwd/dgrad)");
+  m.def("wconv_mm", &wconv_mm,
+        "task-batched bf16 MFMA 3x3 conv fwd/dgrad, 65..256 channels");
+  m.def("wconv_wgrad", &wconv_wgrad,
+        "wide-channel bf16 3x3 conv weight/bias grads (ordered split-K)");
+  m.def("wconv_wgrad_plan", &wconv_wgrad_plan,
+        "wconv_wgrad's split-K plan for a shape: (kchunk, chunks)");
   m.def("gavgpool_fwd", &gavgpool_fwd, "NHWC global average pool fwd");
   m.def("gavgpool_bwd", &gavgpool_bwd, "NHWC global average pool bwd");
   m.def("adam_step",&adam_step, "fused multi-tensor Adam + grad clamp");

@@ -21,6 +21,12 @@ constexpr long kBlocks = 1024;       // grid the chunks are sized for
 constexpr long kBlocksF32 = 3072;
 constexpr long kAtomicCap = 4096;    // longest K-chunk on the atomic path
 constexpr long kNoCap = 0;
+// wconv_wgrad_kernel (wide channels): 128 x 128 tiles, 32-position K-steps
+constexpr int kTileWide = 128;
+constexpr int kStepWide = 32;
+constexpr long kChunkWide = 1024;           // chunk length aimed at
+constexpr long kBlocksWide = 512;           // no more chunks once the grid has these
+constexpr long kSliceBytesWide = 256L << 20;  // cap of the slice buffer
 
 // v2's operand transposes are fixed cost: below this many positions per
 // task the v1 gather kernel wins (hip_autograd.py routes on the same number)
@@ -139,6 +145,32 @@ inline Plan fconv(int T, int NB, int Ho, int Wo, int C) {
   p.Kr = (long)NB * Ho * Wo;
   return with_chunks(p, chunks(p.Kr, (long)p.gridx * T, kStepF32,
                                kBlocksF32));
+}
+
+// wconv_wgrad: always ordered private slices.  The chunk count comes from
+// the reduction length (chunks of about kChunkWide positions), is not raised
+// past what fills the grid — F tiles x column tiles x T blocks often do
+// already, and every chunk costs a slice of 9CF floats per task to write
+// and re-read — and is capped so the slice buffer T * chunks * 9CF * 4 bytes
+// stays within kSliceBytesWide (at C = F = 256 and 128 tasks one chunk alone
+// is 302 MB: no split).
+inline Plan wconv(int T, int NB, int Ho, int Wo, int C, int F) {
+  Plan p{};
+  p.nsub = kTileWide / kCols;
+  p.gridx = (int)(ceil_div(9 * C, kTileWide) * ceil_div(F, kTileWide));
+  p.Wk = Wo;
+  p.Kr = (long)NB * Ho * Wo;
+  const long tasks = T > 1 ? T : 1;
+  const long by_len = ceil_div(p.Kr, kChunkWide);
+  const long by_grid = ceil_div(kBlocksWide, p.gridx * tasks);
+  const long by_bytes = kSliceBytesWide / (tasks * 9 * C * F * 4);
+  long n = by_len < by_grid ? by_len : by_grid;
+  if (n > by_bytes) n = by_bytes;
+  if (n < 1) n = 1;
+  long kchunk = round_up(ceil_div(p.Kr, n), kStepWide);
+  if (kchunk < kStepWide) kchunk = kStepWide;
+  const int gridy = (int)ceil_div(p.Kr > 1 ? p.Kr : 1, kchunk);
+  return with_chunks(p, {(int)kchunk, gridy, gridy});
 }
 
 }  // namespace wgplan

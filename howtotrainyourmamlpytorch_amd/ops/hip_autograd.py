@@ -8,7 +8,8 @@ through the inner-loop support forward):
   derivative order.  There is one trio of Functions; a backend record
   (``_ConvBackend``) names the kernels behind it: bf16 stride 1
   (tconv.hip, wgrad_nt.hip, dconv.hip), bf16 stride 2 of the
-  max_pooling=False backbone (sconv.hip) and fp32 stride 1 (fconv.hip);
+  max_pooling=False backbone (sconv.hip), fp32 stride 1 (fconv.hip) and
+  bf16 stride 1 with 65..256 channels (wconv.hip);
 * BN+act and softmax-CE make their *first backward* its own Function
   whose backward evaluates the analytic closed-form second derivative
   (bn_dbwd.hip / ce_dbwd) — also custom kernels at every order;
@@ -32,9 +33,14 @@ weights, ordered split-K wgrad) and the linear head runs on linear.hip's
 fp32 instantiation, composed like its bf16 twin.  ``MAML355_FCONV=0``
 restores the grouped-ATen conv and ``torch.bmm`` for A/B runs.
 
-Convs with a stride other than 1 or 2, more than 64 channels, or fp32
-compute at stride 2 fall back to the grouped-ATen composition, with a
-warning.
+bf16 stride-1 convs with 8-aligned channels and max(C, F) in 65..256 (wide
+backbones, ``--cnn_num_filters`` above 64) take the wconv.hip backend: one
+128 x 128-tile MFMA kernel for fwd and dgrad and an ordered split-K wgrad.
+``MAML355_WCONV=0`` restores the grouped-ATen composition for A/B runs.
+
+Convs with a stride other than 1 or 2, more than 256 channels, more than 64
+channels that are not 8-aligned, at stride 2 or in fp32, or fp32 compute at
+stride 2 fall back to the grouped-ATen composition, with a warning.
 """
 
 from __future__ import annotations
@@ -672,6 +678,40 @@ def _fconv_wgrad(dy, x, pad, with_bias):
 _FCONV = _ConvBackend(_fconv_fwd, _fconv_dgrad, _fconv_wgrad)
 
 
+# ---------------------------------------------------------------------------
+# backend: bf16 stride 1, 65..256 channels — wconv.hip.  One 128 x 128-tile
+# kernel for fwd and dgrad, wgrad always the ordered private-slice reduction
+# (bitwise reproducible in every mode).  No BN-stats epilogue.
+# ---------------------------------------------------------------------------
+def _wconv_ok(x, w, stride, padding) -> bool:
+    """The wide-channel backend's coverage.  The first layer's C in {1, 3}
+    counts as the 8 channels task_conv3x3 zero-pads it to.  MAML355_WCONV=0
+    restores the grouped-ATen composition (and its warning) for A/B runs."""
+    F, C = w.shape[1], max(w.shape[2], 8)
+    return (x.dtype == torch.bfloat16 and stride == 1 and padding in (0, 1)
+            and C % 8 == 0 and F % 8 == 0 and 64 < max(C, F) <= 256
+            and os.environ.get("MAML355_WCONV", "1") != "0")
+
+
+def _wconv_fwd(x, w, b, pad, want_stats):
+    H, W = x.shape[2], x.shape[3]
+    wp = _ext().wconv_repack(w, False)
+    return _ext().wconv_mm(x, wp, b, pad, H + 2 * pad - 2, W + 2 * pad - 2), None
+
+
+def _wconv_dgrad(dy, w, pad, H, W):
+    """wconv_mm with flipped/transposed repacked weights and pad' = 2 - pad."""
+    wp = _ext().wconv_repack(w, True)
+    return _ext().wconv_mm(dy, wp, None, 2 - pad, H, W)
+
+
+def _wconv_wgrad(dy, x, pad, with_bias):
+    return _ext().wconv_wgrad(dy, x, pad, with_bias)
+
+
+_WCONV = _ConvBackend(_wconv_fwd, _wconv_dgrad, _wconv_wgrad)
+
+
 _FALLBACK_WARNED = set()
 
 
@@ -702,8 +742,10 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False,
             return y, torch.empty(0, device=x.device, dtype=torch.float32)
         return y
     strided_ok = stride == 2 and padding in (0, 1)
-    if (not (stride == 1 or strided_ok) or x.dtype != torch.bfloat16
-            or w.shape[1] > 64 or w.shape[2] > 64):
+    wide = _wconv_ok(x, w, stride, padding)
+    if not wide and (not (stride == 1 or strided_ok)
+                     or x.dtype != torch.bfloat16
+                     or w.shape[1] > 64 or w.shape[2] > 64):
         # strides other than 1/2, fp32 compute and >64-channel shapes use
         # the grouped-ATen composition; loud, not silent
         if not (stride == 1 or strided_ok):
@@ -734,6 +776,16 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False,
         # differentiable, so dw/dx slicing back to C channels is automatic.
         x = torch.nn.functional.pad(x, (0, 8 - C))
         w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 8 - C))
+    if wide:
+        # 65..256 channels: the 128 x 128-tile trio.  No BN-stats epilogue:
+        # return_stats yields empty sums and the BN kernels compute their
+        # own statistics, as on the fp32 path.
+        y = _ConvFwdFn.apply(_WCONV, x.contiguous(), w.float().contiguous(),
+                             b.float().contiguous() if b is not None else None,
+                             padding, False)[0]
+        if return_stats:
+            return y, torch.empty(0, device=x.device, dtype=torch.float32)
+        return y
     y, sums = _ConvFwdFn.apply(_TCONV, x.contiguous(), w.contiguous(),
                                b.contiguous() if b is not None else None,
                                padding, return_stats, xpad)

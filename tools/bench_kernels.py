@@ -10,6 +10,8 @@
     python tools/bench_kernels.py --fconv           # fp32 conv trio vs grouped ATen
     python tools/bench_kernels.py --fconv-model     # fp32 modes, whole-model A/B
     python tools/bench_kernels.py --bn-pool-dbwd    # support BN+pool bwd / dbwd A/B
+    python tools/bench_kernels.py --wconv           # wide bf16 conv trio vs grouped ATen
+    python tools/bench_kernels.py --wconv-model     # 96 / 128 filters, whole-model A/B
 
 Prints per-kernel time, effective TFLOP/s (conv) or TB/s (memory-bound),
 so optimization effort goes where the roofline says.
@@ -785,9 +787,134 @@ def main_bn_pool_dbwd():
         bench_bn_pool_dbwd(32, 100, hw, hw, 64, f"om-{hw}")
 
 
+def bench_wconv(T, NB, H, W, C, F, tag, pad=1):
+    """Wide bf16 stride-1 conv trio (wconv.hip, through the backend functions
+    the autograd trio calls, repack included) against what MAML355_WCONV=0
+    runs at the same shape: the grouped-ATen forward ``ref.task_conv3x3`` in
+    bf16 and its autograd backward.  Medians of interleaved rounds; per call
+    ms, TF and the share of the byte floor (operands and result once over
+    HBM), plus the largest spread between a variant's rounds."""
+    from howtotrainyourmamlpytorch_amd.ops import hip_autograd as ha
+    from howtotrainyourmamlpytorch_amd.ops import reference as ref
+    dev = torch.device("cuda")
+    first = C < 8   # first layer: padded to 8 channels, no dgrad in the net
+    x = torch.randn(T, NB, H, W, C, device=dev).to(torch.bfloat16)
+    w = torch.randn(T, F, C, 3, 3, device=dev).mul(0.1)
+    b = torch.randn(T, F, device=dev)
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    dy = torch.randn(T, NB, Ho, Wo, F, device=dev).to(torch.bfloat16)
+    flops = 2.0 * T * NB * Ho * Wo * F * 9 * C
+    nbytes = 2.0 * (x.numel() + dy.numel()) + 4.0 * w.numel()
+    xk = torch.nn.functional.pad(x, (0, 8 - C)) if first else x
+    wk = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 8 - C)) if first else w
+
+    xr = x.clone().requires_grad_(True)
+    wr = w.to(torch.bfloat16).requires_grad_(True)
+    br = b.to(torch.bfloat16).requires_grad_(True)
+    yr = ref.task_conv3x3(xr, wr, br, 1, pad)
+
+    def r_fwd():
+        with torch.no_grad():
+            ref.task_conv3x3(x, w.to(torch.bfloat16), b.to(torch.bfloat16), 1, pad)
+
+    pairs = [("fwd", lambda: ha._wconv_fwd(xk, wk, b, pad, False), r_fwd),
+             ("dgrad", lambda: ha._wconv_dgrad(dy, wk, pad, H, W),
+              lambda: torch.autograd.grad(yr, xr, dy, retain_graph=True)),
+             ("wgrad", lambda: ha._wconv_wgrad(dy, xk, pad, True),
+              lambda: torch.autograd.grad(yr, (wr, br), dy, retain_graph=True))]
+    line = f"[wconv {tag}] T{T} NB{NB} {H}x{W} C{C}->F{F}"
+    for name, k, r in pairs:
+        if first and name == "dgrad":
+            line += " | dgrad n/a (image input)"
+            continue
+        reps = max(2, min(20, int(0.05 / timeit(k, reps=1, warmup=1))))
+        tk, tr = [], []
+        for _ in range(3):
+            tk.append(timeit(k, reps=reps, warmup=1))
+            tr.append(timeit(r, reps=max(2, reps // 4), warmup=1))
+        mk, mr = sorted(tk)[1], sorted(tr)[1]
+        spread = max(max(tk) - min(tk), max(tr) - min(tr))
+        line += (f" | {name} kernel {mk*1e3:8.3f}ms {flops/mk/1e12:6.1f}TF "
+                 f"{100*nbytes/HBM_BPS/mk:4.1f}%bytefloor ATen {mr*1e3:8.3f}ms "
+                 f"x{mr/mk:5.2f} spread {spread*1e3:.3f}ms")
+    print(line, flush=True)
+    del x, w, dy, xr, wr, yr, xk, wk
+    torch.cuda.empty_cache()
+
+
+def bench_wconv_model(filters, tasks_per_gpu, steps=2, warmup=1, rounds=3):
+    """Whole-model second-order MSL step of the mini-imagenet workload with
+    ``--cnn_num_filters filters``: the wide kernels against MAML355_WCONV=0,
+    alternating rounds in one process."""
+    import argparse
+    import os
+    import warnings
+    import bench
+    from howtotrainyourmamlpytorch_amd.data import SyntheticEpisodeStream
+    from howtotrainyourmamlpytorch_amd.meta.engine import MAMLFewShotClassifier
+
+    cli = argparse.Namespace(model="maml++_miniimagenet_5w1s",
+                             tasks_per_gpu=tasks_per_gpu, inner_steps=5,
+                             second_order="True")
+    args = bench.build_args(cli, 1)
+    args.cnn_num_filters = filters
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = MAMLFewShotClassifier(
+        im_shape=(2, args.image_channels, args.image_height, args.image_width),
+        device=dev, args=args)
+    stream = SyntheticEpisodeStream(args)
+    batches = [tuple(t.to(dev) for t in b) for b in stream.get_train_batches(2)]
+
+    def run(old):
+        os.environ["MAML355_WCONV"] = "0" if old else "1"
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")   # the A/B side warns
+                for i in range(warmup):
+                    model.run_train_iter(batches[i % 2], epoch=0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(steps):
+                    model.run_train_iter(batches[i % 2], epoch=0)
+                torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps
+        finally:
+            os.environ.pop("MAML355_WCONV", None)
+
+    tk, to = [], []
+    for _ in range(rounds):
+        tk.append(run(False))
+        to.append(run(True))
+    mk, mo = sorted(tk)[len(tk) // 2], sorted(to)[len(to) // 2]
+    rk = " ".join(f"{1/t:.3f}" for t in tk)
+    ro = " ".join(f"{1/t:.3f}" for t in to)
+    print(f"[wconv model {filters} filters] {tasks_per_gpu} tasks/step, 2nd "
+          f"order MSL | kernels {1/mk:.3f} steps/s (rounds {rk}) | "
+          f"MAML355_WCONV=0 {1/mo:.3f} steps/s (rounds {ro}) | x{mo/mk:.2f}",
+          flush=True)
+
+
+def main_wconv(with_model):
+    if "--wconv" in sys.argv:
+        # mini-imagenet 5w1s stage shapes at 96 and 128 filters, 128 tasks:
+        # support pass (5 images), then target pass (75 images)
+        for nb, who in ((5, "sup"), (75, "tgt")):
+            for f in (96, 128):
+                bench_wconv(128, nb, 84, 84, 3, f, f"mi{f}-s0-{who}")
+                for hw, st in ((42, 1), (21, 2), (10, 3)):
+                    bench_wconv(128, nb, hw, hw, f, f, f"mi{f}-s{st}-{who}")
+    if with_model:
+        bench_wconv_model(96, 32)
+        bench_wconv_model(128, 32)
+
+
 def main():
     assert torch.cuda.is_available()
     print(torch.cuda.get_device_name(0))
+    if "--wconv" in sys.argv or "--wconv-model" in sys.argv:
+        main_wconv("--wconv-model" in sys.argv)
+        return
     if "--bn-pool-dbwd" in sys.argv:
         main_bn_pool_dbwd()
         return
