@@ -33,6 +33,7 @@ SOURCES = [
     os.path.join(HIP_DIR, "layernorm.hip"),
     os.path.join(HIP_DIR, "fconv.hip"),
     os.path.join(HIP_DIR, "wconv.hip"),
+    os.path.join(HIP_DIR, "wfconv.hip"),
 ]
 
 

@@ -114,6 +114,14 @@ std::vector<torch::Tensor> wconv_wgrad(torch::Tensor dy, torch::Tensor x,
                                        long pad, bool with_bias);
 std::vector<long> wconv_wgrad_plan(long T, long NB, long Ho, long Wo, long C,
                                    long F);
+// wfconv.hip (weights repacked by fconv_repack)
+torch::Tensor wfconv_mm(torch::Tensor x, torch::Tensor wp,
+                        c10::optional<torch::Tensor> bias, long pad,
+                        long Ho, long Wo);
+std::vector<torch::Tensor> wfconv_wgrad(torch::Tensor dy, torch::Tensor x,
+                                        long pad, bool with_bias);
+std::vector<long> wfconv_wgrad_plan(long T, long NB, long Ho, long Wo, long C,
+                                    long F);
 // gavgpool.hip
 torch::Tensor gavgpool_fwd(torch::Tensor x);
 torch::Tensor gavgpool_bwd(torch::Tensor dy, long H, long W);
@@ -189,6 +197,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "wide-channel bf16 3x3 conv weight/bias grads (ordered split-K)");
   m.def("wconv_wgrad_plan", &wconv_wgrad_plan,
         "wconv_wgrad's split-K plan for a shape: (kchunk, chunks)");
+  m.def("wfconv_mm", &wfconv_mm,
+        "task-batched fp32 MFMA 3x3 conv fwd/dgrad, 65..256 channels");
+  m.def("wfconv_wgrad", &wfconv_wgrad,
+        "wide-channel fp32 3x3 conv weight/bias grads (ordered split-K)");
+  m.def("wfconv_wgrad_plan", &wfconv_wgrad_plan,
+        "wfconv_wgrad's split-K plan for a shape: (kchunk, chunks)");
   m.def("gavgpool_fwd", &gavgpool_fwd, "NHWC global average pool fwd");
   m.def("gavgpool_bwd", &gavgpool_bwd, "NHWC global average pool bwd");
   m.def("adam_step",&adam_step, "fused multi-tensor Adam + grad clamp");

@@ -8,8 +8,9 @@ through the inner-loop support forward):
   derivative order.  There is one trio of Functions; a backend record
   (``_ConvBackend``) names the kernels behind it: bf16 stride 1
   (tconv.hip, wgrad_nt.hip, dconv.hip), bf16 stride 2 of the
-  max_pooling=False backbone (sconv.hip), fp32 stride 1 (fconv.hip) and
-  bf16 stride 1 with 65..256 channels (wconv.hip);
+  max_pooling=False backbone (sconv.hip), fp32 stride 1 (fconv.hip), bf16
+  stride 1 with 65..256 channels (wconv.hip) and fp32 stride 1 with 65..256
+  channels (wfconv.hip);
 * BN+act and softmax-CE make their *first backward* its own Function
   whose backward evaluates the analytic closed-form second derivative
   (bn_dbwd.hip / ce_dbwd) — also custom kernels at every order;
@@ -38,8 +39,14 @@ backbones, ``--cnn_num_filters`` above 64) take the wconv.hip backend: one
 128 x 128-tile MFMA kernel for fwd and dgrad and an ordered split-K wgrad.
 ``MAML355_WCONV=0`` restores the grouped-ATen composition for A/B runs.
 
+fp32 stride-1 convs with max(C, F) in 65..256 take the wfconv.hip backend:
+fconv.hip's contract (any C and F, unrounded weights, bitwise repeatable) on
+a flat-K kernel whose waves split the positions only and whose column blocks
+are even.  ``MAML355_WFCONV=0`` restores the grouped-ATen composition for
+them; ``MAML355_FCONV=0`` switches this path off too.
+
 Convs with a stride other than 1 or 2, more than 256 channels, more than 64
-channels that are not 8-aligned, at stride 2 or in fp32, or fp32 compute at
+bf16 channels that are not 8-aligned or at stride 2, or fp32 compute at
 stride 2 fall back to the grouped-ATen composition, with a warning.
 """
 
@@ -712,6 +719,51 @@ def _wconv_wgrad(dy, x, pad, with_bias):
 _WCONV = _ConvBackend(_wconv_fwd, _wconv_dgrad, _wconv_wgrad)
 
 
+# ---------------------------------------------------------------------------
+# backend: fp32 stride 1, 65..256 channels — wfconv.hip.  fconv.hip's
+# contract (unrounded weights, any C and F, no channel padding, ordered
+# private-slice wgrad: bitwise reproducible in every mode) at wide channels;
+# the weights are repacked by fconv_repack.  No BN-stats epilogue.
+# ---------------------------------------------------------------------------
+def _wfconv_on() -> bool:
+    """MAML355_WFCONV=0 restores the grouped-ATen composition (and its
+    warning) for fp32 convs above 64 channels, for A/B runs."""
+    return os.environ.get("MAML355_WFCONV", "1") != "0"
+
+
+def _wfconv_fwd(x, w, b, pad, want_stats):
+    H, W = x.shape[2], x.shape[3]
+    wp = _ext().fconv_repack(w, False)
+    return _ext().wfconv_mm(x, wp, b, pad, H + 2 * pad - 2, W + 2 * pad - 2), None
+
+
+def _wfconv_dgrad(dy, w, pad, H, W):
+    """wfconv_mm with flipped/transposed repacked weights and pad' = 2 - pad."""
+    wp = _ext().fconv_repack(w, True)
+    return _ext().wfconv_mm(dy, wp, None, 2 - pad, H, W)
+
+
+def _wfconv_wgrad(dy, x, pad, with_bias):
+    return _ext().wfconv_wgrad(dy, x, pad, with_bias)
+
+
+_WFCONV = _ConvBackend(_wfconv_fwd, _wfconv_dgrad, _wfconv_wgrad)
+
+
+def _fp32_backend(x, w, stride, padding):
+    """The fp32 stride-1 backend for a conv — fconv.hip up to 64 channels,
+    wfconv.hip for max(C, F) in 65..256 — or None where fp32 falls back."""
+    if not (x.dtype == torch.float32 and stride == 1 and padding in (0, 1)
+            and _fconv_on()):
+        return None
+    widest = max(w.shape[1], w.shape[2])
+    if widest <= 64:
+        return _FCONV
+    if widest <= 256 and _wfconv_on():
+        return _WFCONV
+    return None
+
+
 _FALLBACK_WARNED = set()
 
 
@@ -730,12 +782,12 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False,
     # w is task-batched [T, F, C, 3, 3]: dim 1 = out-channels, dim 2 = in
     # xpad: PreparedInput.xpad of x, only ever given for the bf16 stride-1
     # first layer (prepare_conv_input returns None for everything else)
-    if (x.dtype == torch.float32 and stride == 1 and padding in (0, 1)
-            and w.shape[1] <= 64 and w.shape[2] <= 64 and _fconv_on()):
+    fp32_be = _fp32_backend(x, w, stride, padding)
+    if fp32_be is not None:
         # fp32 activations: the fp32 MFMA trio, weights and bias unrounded.
         # No BN-stats epilogue: return_stats yields empty sums and the BN
         # kernels compute their own statistics, as on the stride-2 path.
-        y = _ConvFwdFn.apply(_FCONV, x.contiguous(), w.float().contiguous(),
+        y = _ConvFwdFn.apply(fp32_be, x.contiguous(), w.float().contiguous(),
                              b.float().contiguous() if b is not None else None,
                              padding, False)[0]
         if return_stats:

@@ -12,6 +12,8 @@
     python tools/bench_kernels.py --bn-pool-dbwd    # support BN+pool bwd / dbwd A/B
     python tools/bench_kernels.py --wconv           # wide bf16 conv trio vs grouped ATen
     python tools/bench_kernels.py --wconv-model     # 96 / 128 filters, whole-model A/B
+    python tools/bench_kernels.py --wfconv          # wide fp32 conv trio vs grouped ATen
+    python tools/bench_kernels.py --wfconv-model    # 96 / 128 filters, fp32 modes, A/B
 
 Prints per-kernel time, effective TFLOP/s (conv) or TB/s (memory-bound),
 so optimization effort goes where the roofline says.
@@ -909,9 +911,147 @@ def main_wconv(with_model):
         bench_wconv_model(128, 32)
 
 
+def bench_wfconv(T, NB, H, W, C, F, tag, pad=1):
+    """Wide fp32 stride-1 conv trio (wfconv.hip, through the backend functions
+    the autograd trio calls, repack included) against what MAML355_WFCONV=0
+    runs at the same shape: the grouped-ATen forward ``ref.task_conv3x3`` in
+    fp32 and its autograd backward.  Medians of interleaved rounds; per call
+    ms, TF, the share of the fp32 matrix peak and of the byte floor, plus the
+    largest spread between a variant's rounds."""
+    from howtotrainyourmamlpytorch_amd.ops import hip_autograd as ha
+    from howtotrainyourmamlpytorch_amd.ops import reference as ref
+    dev = torch.device("cuda")
+    first = C < 8   # first layer: no dgrad in the net (x is the image)
+    x = torch.randn(T, NB, H, W, C, device=dev)
+    w = torch.randn(T, F, C, 3, 3, device=dev).mul(0.1)
+    b = torch.randn(T, F, device=dev)
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    dy = torch.randn(T, NB, Ho, Wo, F, device=dev)
+    flops = 2.0 * T * NB * Ho * Wo * F * 9 * C
+    nbytes = 4.0 * (x.numel() + dy.numel() + w.numel())
+
+    xr = x.clone().requires_grad_(True)
+    wr = w.clone().requires_grad_(True)
+    br = b.clone().requires_grad_(True)
+    yr = ref.task_conv3x3(xr, wr, br, 1, pad)
+
+    def r_fwd():
+        with torch.no_grad():
+            ref.task_conv3x3(x, w, b, 1, pad)
+
+    pairs = [("fwd", lambda: ha._wfconv_fwd(x, w, b, pad, False), r_fwd),
+             ("dgrad", lambda: ha._wfconv_dgrad(dy, w, pad, H, W),
+              lambda: torch.autograd.grad(yr, xr, dy, retain_graph=True)),
+             ("wgrad", lambda: ha._wfconv_wgrad(dy, x, pad, True),
+              lambda: torch.autograd.grad(yr, (wr, br), dy, retain_graph=True))]
+    line = f"[wfconv {tag}] T{T} NB{NB} {H}x{W} C{C}->F{F}"
+    for name, k, r in pairs:
+        if first and name == "dgrad":
+            line += " | dgrad n/a (image input)"
+            continue
+        reps = max(2, min(20, int(0.05 / timeit(k, reps=1, warmup=1))))
+        tk, tr = [], []
+        for _ in range(3):
+            tk.append(timeit(k, reps=reps, warmup=1))
+            tr.append(timeit(r, reps=max(2, reps // 4), warmup=1))
+        mk, mr = sorted(tk)[1], sorted(tr)[1]
+        spread = max(max(tk) - min(tk), max(tr) - min(tr))
+        line += (f" | {name} kernel {mk*1e3:8.3f}ms {flops/mk/1e12:6.1f}TF "
+                 f"{100*flops/mk/FP32_MATRIX_PEAK:4.1f}%peak "
+                 f"{100*nbytes/HBM_BPS/mk:4.1f}%bytefloor ATen {mr*1e3:8.3f}ms "
+                 f"x{mr/mk:5.2f} spread {spread*1e3:.3f}ms")
+    print(line, flush=True)
+    del x, w, dy, xr, wr, yr
+    torch.cuda.empty_cache()
+
+
+def bench_wfconv_model(filters, tasks_per_gpu, mode, steps=2, warmup=1,
+                       rounds=3):
+    """Whole-model second-order MSL step of the mini-imagenet workload with
+    ``--cnn_num_filters filters`` and fp32 activations (``mode``: "support" =
+    --fp32_support_pass True, "fp32" = --compute_dtype fp32): the wide fp32
+    kernels against MAML355_WFCONV=0, alternating rounds in one process."""
+    import argparse
+    import os
+    import warnings
+    import bench
+    from howtotrainyourmamlpytorch_amd.data import SyntheticEpisodeStream
+    from howtotrainyourmamlpytorch_amd.meta.engine import MAMLFewShotClassifier
+
+    cli = argparse.Namespace(model="maml++_miniimagenet_5w1s",
+                             tasks_per_gpu=tasks_per_gpu, inner_steps=5,
+                             second_order="True")
+    args = bench.build_args(cli, 1)
+    args.cnn_num_filters = filters
+    if mode == "support":
+        args.fp32_support_pass = True
+    else:
+        args.compute_dtype = "fp32"
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = MAMLFewShotClassifier(
+        im_shape=(2, args.image_channels, args.image_height, args.image_width),
+        device=dev, args=args)
+    stream = SyntheticEpisodeStream(args)
+    batches = [tuple(t.to(dev) for t in b) for b in stream.get_train_batches(2)]
+
+    def run(old):
+        os.environ["MAML355_WFCONV"] = "0" if old else "1"
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")   # the A/B side warns
+                for i in range(warmup):
+                    model.run_train_iter(batches[i % 2], epoch=0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(steps):
+                    model.run_train_iter(batches[i % 2], epoch=0)
+                torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps
+        finally:
+            os.environ.pop("MAML355_WFCONV", None)
+
+    tk, to = [], []
+    try:
+        for _ in range(rounds):
+            tk.append(run(False))
+            to.append(run(True))
+    except torch.cuda.OutOfMemoryError:
+        print(f"[wfconv model {filters} filters {mode}] {tasks_per_gpu} "
+              f"tasks/step: out of memory (kernel runs so far: {tk})", flush=True)
+        return
+    mk, mo = sorted(tk)[len(tk) // 2], sorted(to)[len(to) // 2]
+    rk = " ".join(f"{1/t:.3f}" for t in tk)
+    ro = " ".join(f"{1/t:.3f}" for t in to)
+    print(f"[wfconv model {filters} filters {mode}] {tasks_per_gpu} tasks/step, "
+          f"2nd order MSL | kernels {1/mk:.3f} steps/s (rounds {rk}) | "
+          f"MAML355_WFCONV=0 {1/mo:.3f} steps/s (rounds {ro}) | x{mo/mk:.2f}",
+          flush=True)
+
+
+def main_wfconv(with_model):
+    if "--wfconv" in sys.argv:
+        # mini-imagenet 5w1s support-pass stage shapes (5 images) at 128
+        # tasks, 96 and 128 filters; fconv at 48 filters and the same spatial
+        # shapes first, so the effect of the wider tile can be read directly
+        for hw, st in ((42, 1), (21, 2), (10, 3)):
+            bench_fconv(128, 5, hw, hw, 48, 48, f"mi48-s{st}-sup")
+        for f in (96, 128):
+            bench_wfconv(128, 5, 84, 84, 3, f, f"mi{f}-s0-sup")
+            for hw, st in ((42, 1), (21, 2), (10, 3)):
+                bench_wfconv(128, 5, hw, hw, f, f, f"mi{f}-s{st}-sup")
+    if with_model:
+        for mode in ("support", "fp32"):
+            bench_wfconv_model(96, 32, mode)
+            bench_wfconv_model(128, 32, mode)
+
+
 def main():
     assert torch.cuda.is_available()
     print(torch.cuda.get_device_name(0))
+    if "--wfconv" in sys.argv or "--wfconv-model" in sys.argv:
+        main_wfconv("--wfconv-model" in sys.argv)
+        return
     if "--wconv" in sys.argv or "--wconv-model" in sys.argv:
         main_wconv("--wconv-model" in sys.argv)
         return
