@@ -54,6 +54,36 @@ def linear(x, w, b=None):
     return y if b is None else y + b.unsqueeze(1)
 
 
+def softmax_ce(logits, labels):
+    """Per-task mean of ``logsumexp - l[y]``: logits [T, M, ways], labels
+    [T, M] (any integer type) -> [T]."""
+    lse = torch.logsumexp(logits, dim=-1)
+    ly = logits.gather(-1, labels.long().unsqueeze(-1)).squeeze(-1)
+    return (lse - ly).mean(dim=1)
+
+
+def lslr(arena, grad, lr_vec):
+    """``arena - lr_vec * grad``: arena/grad [T, P], lr_vec [P]."""
+    return arena - lr_vec.unsqueeze(0) * grad
+
+
+def adam_step(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay=0.0,
+              clamp=None):
+    """One Adam step, pure: returns the new ``(p, m, v)``.  The gradient is
+    clamped first, then the decay ``weight_decay * p`` is added — the order
+    of adam.hip and ``ops.reference``.  Bias corrections in double."""
+    if clamp is not None:
+        g = g.clamp(-clamp, clamp)
+    if weight_decay != 0.0:
+        g = g + weight_decay * p
+    m = beta1 * m + (1.0 - beta1) * g
+    v = beta2 * v + (1.0 - beta2) * g * g
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    denom = (v / bc2).sqrt() + eps
+    return p - (lr / bc1) * m / denom, m, v
+
+
 def _affine(p, T, C):
     return p.view(1, 1, 1, 1, C) if p.dim() == 1 else p.view(T, 1, 1, 1, C)
 
@@ -182,3 +212,116 @@ def assert_close(got, ref, rtol, atol, keep=None, name="value"):
 def assert_f32_close(got, ref, name="value"):
     assert got.dtype == torch.float32, (name, got.dtype)
     assert_close(got, ref, F32_RTOL, F32_ATOL, name=name)
+
+
+# ---------------------------------------------------------------------------
+# derived bounds of the head, loss and update kernels (fp32 arithmetic,
+# unit roundoff EPS32 = 2^-24), all against the float64 functions above
+# ---------------------------------------------------------------------------
+EPS32 = 2.0 ** -24
+
+
+def assert_within(got, ref, bound, name="value"):
+    """|got - ref| <= bound elementwise, every element compared; a zero
+    bound demands equality.  Returns the worst err/bound."""
+    got = got.detach().to("cpu").to(F64)
+    ref = ref.detach().to(F64)
+    bound = bound.detach().to(F64).expand_as(ref)
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    err = (got - ref).abs()
+    exact = bound == 0
+    assert (err[exact] == 0).all().item(), f"{name}: nonzero error at a zero bound"
+    worst = _report(name, err[~exact], bound[~exact])
+    assert worst <= 1.0, f"{name}: err/bound {worst:.3f}"
+    return worst
+
+
+def dot_bound(mag, n, ref=None):
+    """An fp32 dot product of length n, summed in any order with or without
+    fma: ``(n + 2) 2^-24 sum|a||b|`` (``mag`` is that sum).  With ``ref``
+    the result is then rounded to bf16: one more ``2^-8 |ref|``."""
+    bound = (n + 2) * EPS32 * mag
+    return bound if ref is None else bound + BF16_ULP * ref.abs()
+
+
+def assert_dot_bounded(got, ref, mag, n, name, bf16=False):
+    assert got.dtype == (torch.bfloat16 if bf16 else torch.float32), (name, got.dtype)
+    return assert_within(got, ref, dot_bound(mag, n, ref if bf16 else None),
+                         f"{name} (n={n})")
+
+
+CE_RTOL = CE_ATOL = 1e-5      # test_ce_fwd_bwd_and_create_graph's figures
+
+
+def ce_loss_bound(ref, logits):
+    """[T]: the N(0,1) figure plus the cancellation of ``log(se) + max -
+    l[y]``, whose middle sum is rounded at the size of the logits:
+    ``2^-23 max|logit|`` over the task."""
+    return (CE_ATOL + CE_RTOL * ref.abs()
+            + 2 * EPS32 * logits.detach().abs().amax(dim=(1, 2)))
+
+
+def ce_prob_bound(ref, logits, bf16=False):
+    """Anything linear in the softmax probabilities.  ``exp(v - max)`` is
+    evaluated as ``exp2((v - max) * log2 e)``; the product's rounding is a
+    relative error ``|v - max| 2^-24`` of the result, twice that with the
+    constant's own: ``2^-23 max_row|logit - max| |ref|`` on top of the
+    N(0,1) figure.  ``ref`` is [T, M, ways] (per row) or [T] (per task)."""
+    lg = logits.detach()
+    spread = lg.amax(dim=-1) - lg.amin(dim=-1)             # [T, M]
+    spread = spread.unsqueeze(-1) if ref.dim() == 3 else spread.amax(dim=1)
+    bound = CE_ATOL + (CE_RTOL + 2 * EPS32 * spread) * ref.abs()
+    return bound + BF16_ULP * ref.abs() if bf16 else bound
+
+
+def adam_bias_terms(beta1, beta2, step):
+    """(d1, d2, e_bc) for ``1 - powf(beta, step)`` formed in fp32:
+    ``d = beta^step (step + 2) 2^-24`` for the power plus ``2^-24 bc`` for
+    the rounding of the subtraction — all that is left of the error once
+    ``beta^step`` has dropped below ulp(1).  ``e_bc = d1/bc1 + d2/(2 bc2)``
+    is the relative error they put on the step size."""
+    out = []
+    for beta in (beta1, beta2):
+        bc = 1.0 - beta ** step
+        out.append((beta ** step * (step + 2) * EPS32 + EPS32 * bc, bc))
+    (d1, bc1), (d2, bc2) = out
+    return d1, d2, d1 / bc1 + d2 / (2.0 * bc2)
+
+
+def adam_bounds(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay=0.0,
+                clamp=None):
+    """Reference and bound of one fp32 Adam step on float64 copies of the
+    kernel's own inputs.  Returns ``((p, m, v), (bound_p, bound_m,
+    bound_v))``.
+
+    With u = 2^-24 and G = |clamp(g)| + |weight_decay p| the magnitude of
+    the gradient the moments see (x = 2 roundings on it with decay, 0
+    without, when it is exact):
+      m: (4 + x) u (|beta1 m0| + (1 - beta1) G)
+      v: (5 + 2x) u (beta2 v0 + (1 - beta2) G^2)         (= 5 u ref without decay)
+      p: u |ref| + dp_mag (e_bc + (8 + 2x) u + (5 + 2x)/2 u (v_mag/v - 1))
+    where dp_mag = lr m_mag / (bc1 denom) is |dp| with the two terms of m
+    taken by magnitude: where they cancel, the error of m is not small next
+    to m itself.  The widening is per element: without decay, wherever
+    beta1 m0 and (1 - beta1) g share a sign (m_mag = |m|, v_mag = v) these
+    are exactly the plain ``4 u (..)``, ``5 u v`` and ``u |ref| + |dp|
+    (e_bc + 8 u)``, which is the case for 53% of the elements of the tests'
+    no-decay inputs.  Elsewhere the p bound grows with m_mag / |m|: on the
+    tests' inputs up to 1440 times the plain one, at single elements where
+    m cancels almost entirely.  The fp32 reference breaks the plain forms
+    there (p by 14.8 at step 100000 from zero params, m by 1.57 under
+    decay)."""
+    ref = adam_step(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, clamp)
+    x = 2 if weight_decay != 0.0 else 0
+    gc = g.clamp(-clamp, clamp) if clamp is not None else g
+    G = gc.abs() + abs(weight_decay) * p.abs()
+    m_mag = (beta1 * m).abs() + (1.0 - beta1) * G
+    v_mag = beta2 * v + (1.0 - beta2) * G * G
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    _, _, e_bc = adam_bias_terms(beta1, beta2, step)
+    dp_mag = lr * m_mag / (bc1 * ((ref[2] / bc2).sqrt() + eps))
+    rv = v_mag / ref[2].clamp_min(1e-300)
+    bound_p = EPS32 * ref[0].abs() + dp_mag * (
+        e_bc + (8 + 2 * x) * EPS32 + 0.5 * (5 + 2 * x) * EPS32 * (rv - 1.0))
+    return ref, (bound_p, (4 + x) * EPS32 * m_mag, (5 + 2 * x) * EPS32 * v_mag)
