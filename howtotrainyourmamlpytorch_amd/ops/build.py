@@ -34,6 +34,7 @@ SOURCES = [
     os.path.join(HIP_DIR, "fconv.hip"),
     os.path.join(HIP_DIR, "wconv.hip"),
     os.path.join(HIP_DIR, "wfconv.hip"),
+    os.path.join(HIP_DIR, "swconv.hip"),
 ]
 
 

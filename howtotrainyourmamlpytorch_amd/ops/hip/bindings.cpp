@@ -114,6 +114,13 @@ std::vector<torch::Tensor> wconv_wgrad(torch::Tensor dy, torch::Tensor x,
                                        long pad, bool with_bias);
 std::vector<long> wconv_wgrad_plan(long T, long NB, long Ho, long Wo, long C,
                                    long F);
+// swconv.hip (weights repacked by wconv_repack)
+torch::Tensor swconv_fwd(torch::Tensor x, torch::Tensor wp,
+                         c10::optional<torch::Tensor> bias, long pad);
+torch::Tensor swconv_dgrad(torch::Tensor dy, torch::Tensor wp, long pad,
+                           long H, long W);
+std::vector<torch::Tensor> swconv_wgrad(torch::Tensor dy, torch::Tensor x,
+                                        long pad, bool with_bias);
 // wfconv.hip (weights repacked by fconv_repack)
 torch::Tensor wfconv_mm(torch::Tensor x, torch::Tensor wp,
                         c10::optional<torch::Tensor> bias, long pad,
@@ -197,6 +204,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "wide-channel bf16 3x3 conv weight/bias grads (ordered split-K)");
   m.def("wconv_wgrad_plan", &wconv_wgrad_plan,
         "wconv_wgrad's split-K plan for a shape: (kchunk, chunks)");
+  m.def("swconv_fwd", &swconv_fwd,
+        "task-batched bf16 MFMA stride-2 3x3 conv fwd, 65..256 channels");
+  m.def("swconv_dgrad", &swconv_dgrad,
+        "wide-channel stride-2 3x3 conv input-grad (four parity sub-GEMMs)");
+  m.def("swconv_wgrad", &swconv_wgrad,
+        "wide-channel stride-2 3x3 conv weight/bias grads (ordered split-K)");
   m.def("wfconv_mm", &wfconv_mm,
         "task-batched fp32 MFMA 3x3 conv fwd/dgrad, 65..256 channels");
   m.def("wfconv_wgrad", &wfconv_wgrad,

@@ -9,8 +9,9 @@ through the inner-loop support forward):
   (``_ConvBackend``) names the kernels behind it: bf16 stride 1
   (tconv.hip, wgrad_nt.hip, dconv.hip), bf16 stride 2 of the
   max_pooling=False backbone (sconv.hip), fp32 stride 1 (fconv.hip), bf16
-  stride 1 with 65..256 channels (wconv.hip) and fp32 stride 1 with 65..256
-  channels (wfconv.hip);
+  stride 1 with 65..256 channels (wconv.hip), fp32 stride 1 with 65..256
+  channels (wfconv.hip) and bf16 stride 2 with 65..256 channels
+  (swconv.hip);
 * BN+act and softmax-CE make their *first backward* its own Function
   whose backward evaluates the analytic closed-form second derivative
   (bn_dbwd.hip / ce_dbwd) — also custom kernels at every order;
@@ -45,9 +46,17 @@ a flat-K kernel whose waves split the positions only and whose column blocks
 are even.  ``MAML355_WFCONV=0`` restores the grouped-ATen composition for
 them; ``MAML355_FCONV=0`` switches this path off too.
 
+bf16 stride-2 convs with 8-aligned channels and max(C, F) in 65..256 (the
+max_pooling=False backbone above 64 filters) take the swconv.hip backend:
+wconv.hip's 128 x 128 tile and numerics on sconv.hip's geometry — a
+four-edge-predicated stride-2 gather for fwd and wgrad, four parity
+sub-GEMMs in one launch for dgrad, ordered split-K wgrad.  Bitwise
+repeatable in every mode.  ``MAML355_SWCONV=0`` restores the grouped-ATen
+composition for A/B runs.
+
 Convs with a stride other than 1 or 2, more than 256 channels, more than 64
-bf16 channels that are not 8-aligned or at stride 2, or fp32 compute at
-stride 2 fall back to the grouped-ATen composition, with a warning.
+bf16 channels that are not 8-aligned, or fp32 compute at stride 2 fall back
+to the grouped-ATen composition, with a warning.
 """
 
 from __future__ import annotations
@@ -750,6 +759,41 @@ def _wfconv_wgrad(dy, x, pad, with_bias):
 _WFCONV = _ConvBackend(_wfconv_fwd, _wfconv_dgrad, _wfconv_wgrad)
 
 
+# ---------------------------------------------------------------------------
+# backend: bf16 stride 2, 65..256 channels — swconv.hip.  fwd reads
+# wconv_repack's plain image, dgrad (four parity sub-GEMMs, one launch) its
+# flipped one, wgrad is the ordered private-slice reduction over the output
+# positions (bitwise reproducible in every mode).  No BN-stats epilogue.
+# ---------------------------------------------------------------------------
+def _swconv_ok(x, w, stride, padding) -> bool:
+    """The wide stride-2 backend's coverage: _wconv_ok's with stride 2.  The
+    first layer's C in {1, 3} counts as the 8 channels task_conv3x3 zero-pads
+    it to.  MAML355_SWCONV=0 restores the grouped-ATen composition (and its
+    warning) for A/B runs."""
+    F, C = w.shape[1], max(w.shape[2], 8)
+    return (x.dtype == torch.bfloat16 and stride == 2 and padding in (0, 1)
+            and C % 8 == 0 and F % 8 == 0 and 64 < max(C, F) <= 256
+            and os.environ.get("MAML355_SWCONV", "1") != "0")
+
+
+def _swconv_fwd(x, w, b, pad, want_stats):
+    wp = _ext().wconv_repack(w, False)
+    return _ext().swconv_fwd(x, wp, b, pad), None
+
+
+def _swconv_dgrad(dy, w, pad, H, W):
+    """The parity kernels index the flipped image's taps at 8 - (3 ky + kx)."""
+    wp = _ext().wconv_repack(w, True)
+    return _ext().swconv_dgrad(dy, wp, pad, H, W)
+
+
+def _swconv_wgrad(dy, x, pad, with_bias):
+    return _ext().swconv_wgrad(dy, x, pad, with_bias)
+
+
+_SWCONV = _ConvBackend(_swconv_fwd, _swconv_dgrad, _swconv_wgrad)
+
+
 def _fp32_backend(x, w, stride, padding):
     """The fp32 stride-1 backend for a conv — fconv.hip up to 64 channels,
     wfconv.hip for max(C, F) in 65..256 — or None where fp32 falls back."""
@@ -795,9 +839,10 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False,
         return y
     strided_ok = stride == 2 and padding in (0, 1)
     wide = _wconv_ok(x, w, stride, padding)
-    if not wide and (not (stride == 1 or strided_ok)
-                     or x.dtype != torch.bfloat16
-                     or w.shape[1] > 64 or w.shape[2] > 64):
+    swide = _swconv_ok(x, w, stride, padding)
+    if not (wide or swide) and (not (stride == 1 or strided_ok)
+                                or x.dtype != torch.bfloat16
+                                or w.shape[1] > 64 or w.shape[2] > 64):
         # strides other than 1/2, fp32 compute and >64-channel shapes use
         # the grouped-ATen composition; loud, not silent
         if not (stride == 1 or strided_ok):
@@ -818,9 +863,17 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False,
         if C < 8:
             x = torch.nn.functional.pad(x, (0, 8 - C))
             w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 8 - C))
-        y = _ConvFwdFn.apply(_SCONV, x.contiguous(), w.contiguous(),
-                             b.contiguous() if b is not None else None,
-                             padding, False)[0]
+        if swide:
+            # 65..256 channels: the 128 x 128-tile stride-2 trio, weights
+            # and bias fp32 as on the wide stride-1 branch
+            y = _ConvFwdFn.apply(_SWCONV, x.contiguous(),
+                                 w.float().contiguous(),
+                                 b.float().contiguous() if b is not None
+                                 else None, padding, False)[0]
+        else:
+            y = _ConvFwdFn.apply(_SCONV, x.contiguous(), w.contiguous(),
+                                 b.contiguous() if b is not None else None,
+                                 padding, False)[0]
         return (y, None) if return_stats else y
     if C < 8 and not _dconv_ok(C, F):
         # small C without a direct-kernel instantiation: zero-pad to 8 so

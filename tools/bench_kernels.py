@@ -14,6 +14,8 @@
     python tools/bench_kernels.py --wconv-model     # 96 / 128 filters, whole-model A/B
     python tools/bench_kernels.py --wfconv          # wide fp32 conv trio vs grouped ATen
     python tools/bench_kernels.py --wfconv-model    # 96 / 128 filters, fp32 modes, A/B
+    python tools/bench_kernels.py --swconv          # wide bf16 stride-2 trio vs grouped ATen
+    python tools/bench_kernels.py --swconv-model    # strided backbone, 96 / 128 filters, A/B
 
 Prints per-kernel time, effective TFLOP/s (conv) or TB/s (memory-bound),
 so optimization effort goes where the roofline says.
@@ -911,6 +913,137 @@ def main_wconv(with_model):
         bench_wconv_model(128, 32)
 
 
+def bench_swconv(T, NB, H, W, C, F, tag, pad=1):
+    """Wide bf16 stride-2 conv trio (swconv.hip, through the backend functions
+    the autograd trio calls, repack included) against what MAML355_SWCONV=0
+    runs at the same shape: the grouped-ATen forward ``ref.task_conv3x3`` in
+    bf16 at stride 2 and its autograd backward.  Medians of 3 alternating
+    rounds with min-max; per call ms, TF and the share of the byte floor
+    (operands and result once over HBM)."""
+    from howtotrainyourmamlpytorch_amd.ops import hip_autograd as ha
+    from howtotrainyourmamlpytorch_amd.ops import reference as ref
+    dev = torch.device("cuda")
+    first = C < 8   # first layer: padded to 8 channels, no dgrad in the net
+    x = torch.randn(T, NB, H, W, C, device=dev).to(torch.bfloat16)
+    w = torch.randn(T, F, C, 3, 3, device=dev).mul(0.1)
+    b = torch.randn(T, F, device=dev)
+    Ho, Wo = (H + 2 * pad - 3) // 2 + 1, (W + 2 * pad - 3) // 2 + 1
+    dy = torch.randn(T, NB, Ho, Wo, F, device=dev).to(torch.bfloat16)
+    flops = 2.0 * T * NB * Ho * Wo * F * 9 * C
+    nbytes = 2.0 * (x.numel() + dy.numel()) + 4.0 * w.numel()
+    xk = torch.nn.functional.pad(x, (0, 8 - C)) if first else x
+    wk = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 8 - C)) if first else w
+
+    xr = x.clone().requires_grad_(True)
+    wr = w.to(torch.bfloat16).requires_grad_(True)
+    br = b.to(torch.bfloat16).requires_grad_(True)
+    yr = ref.task_conv3x3(xr, wr, br, 2, pad)
+
+    def r_fwd():
+        with torch.no_grad():
+            ref.task_conv3x3(x, w.to(torch.bfloat16), b.to(torch.bfloat16), 2, pad)
+
+    pairs = [("fwd", lambda: ha._swconv_fwd(xk, wk, b, pad, False), r_fwd),
+             ("dgrad", lambda: ha._swconv_dgrad(dy, wk, pad, H, W),
+              lambda: torch.autograd.grad(yr, xr, dy, retain_graph=True)),
+             ("wgrad", lambda: ha._swconv_wgrad(dy, xk, pad, True),
+              lambda: torch.autograd.grad(yr, (wr, br), dy, retain_graph=True))]
+    line = f"[swconv {tag}] T{T} NB{NB} {H}x{W}->{Ho}x{Wo} C{C}->F{F}"
+    for name, k, r in pairs:
+        if first and name == "dgrad":
+            line += " | dgrad n/a (image input)"
+            continue
+        reps = max(2, min(20, int(0.05 / timeit(k, reps=1, warmup=1))))
+        tk, tr = [], []
+        for _ in range(3):
+            tk.append(timeit(k, reps=reps, warmup=1))
+            tr.append(timeit(r, reps=max(2, reps // 4), warmup=1))
+        mk, mr = sorted(tk)[1], sorted(tr)[1]
+        line += (f" | {name} kernel {mk*1e3:8.3f}ms ({min(tk)*1e3:.3f}-"
+                 f"{max(tk)*1e3:.3f}) {flops/mk/1e12:6.1f}TF "
+                 f"{100*nbytes/HBM_BPS/mk:4.1f}%bytefloor ATen {mr*1e3:8.3f}ms "
+                 f"({min(tr)*1e3:.3f}-{max(tr)*1e3:.3f}) x{mr/mk:5.2f}")
+    print(line, flush=True)
+    del x, w, dy, xr, wr, yr, xk, wk
+    torch.cuda.empty_cache()
+
+
+def bench_swconv_model(filters, tasks_per_gpu, steps=2, warmup=1, rounds=3):
+    """Whole-model second-order MSL step of the mini-imagenet workload on the
+    strided backbone (``--max_pooling False``) with ``--cnn_num_filters
+    filters``: the wide stride-2 kernels against MAML355_SWCONV=0,
+    alternating rounds in one process."""
+    import argparse
+    import os
+    import warnings
+    import bench
+    from howtotrainyourmamlpytorch_amd.data import SyntheticEpisodeStream
+    from howtotrainyourmamlpytorch_amd.meta.engine import MAMLFewShotClassifier
+
+    cli = argparse.Namespace(model="maml++_miniimagenet_5w1s",
+                             tasks_per_gpu=tasks_per_gpu, inner_steps=5,
+                             second_order="True")
+    args = bench.build_args(cli, 1)
+    args.cnn_num_filters = filters
+    args.max_pooling = False
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = MAMLFewShotClassifier(
+        im_shape=(2, args.image_channels, args.image_height, args.image_width),
+        device=dev, args=args)
+    assert not model.classifier.max_pooling
+    stream = SyntheticEpisodeStream(args)
+    batches = [tuple(t.to(dev) for t in b) for b in stream.get_train_batches(2)]
+
+    def run(old):
+        os.environ["MAML355_SWCONV"] = "0" if old else "1"
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")   # the A/B side warns
+                for i in range(warmup):
+                    model.run_train_iter(batches[i % 2], epoch=0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(steps):
+                    model.run_train_iter(batches[i % 2], epoch=0)
+                torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps
+        finally:
+            os.environ.pop("MAML355_SWCONV", None)
+
+    tk, to = [], []
+    for _ in range(rounds):
+        tk.append(run(False))
+        to.append(run(True))
+    mk, mo = sorted(tk)[len(tk) // 2], sorted(to)[len(to) // 2]
+    n = tasks_per_gpu
+    rk = " ".join(f"{n/t:.1f}" for t in tk)
+    ro = " ".join(f"{n/t:.1f}" for t in to)
+    print(f"[swconv model {filters} filters, strided] {n} tasks/step, 2nd "
+          f"order MSL | kernels {n/mk:.1f} tasks/s (rounds {rk}) | "
+          f"MAML355_SWCONV=0 {n/mo:.1f} tasks/s (rounds {ro}) | x{mo/mk:.2f}",
+          flush=True)
+
+
+def main_swconv(with_model):
+    if "--swconv" in sys.argv:
+        # strided-backbone stage shapes at 96 and 128 filters, support pass
+        # then target pass: mini-imagenet 5w1s at 128 tasks (5 / 75 images,
+        # 84 -> 42 -> 21 -> 11 -> 6), omniglot 20w5s at 32 tasks (100 / 20
+        # images, 28 -> 14 -> 7 -> 4 -> 2)
+        for T, ch, sizes, passes, name in (
+                (128, 3, (84, 42, 21, 11), ((5, "sup"), (75, "tgt")), "mi"),
+                (32, 1, (28, 14, 7, 4), ((100, "sup"), (20, "tgt")), "om")):
+            for nb, who in passes:
+                for f in (96, 128):
+                    for st, hw in enumerate(sizes):
+                        bench_swconv(T, nb, hw, hw, f if st else ch, f,
+                                     f"{name}{f}-s{st}-{who}")
+    if with_model:
+        bench_swconv_model(96, 32)
+        bench_swconv_model(128, 32)
+
+
 def bench_wfconv(T, NB, H, W, C, F, tag, pad=1):
     """Wide fp32 stride-1 conv trio (wfconv.hip, through the backend functions
     the autograd trio calls, repack included) against what MAML355_WFCONV=0
@@ -1051,6 +1184,9 @@ def main():
     print(torch.cuda.get_device_name(0))
     if "--wfconv" in sys.argv or "--wfconv-model" in sys.argv:
         main_wfconv("--wfconv-model" in sys.argv)
+        return
+    if "--swconv" in sys.argv or "--swconv-model" in sys.argv:
+        main_swconv("--swconv-model" in sys.argv)
         return
     if "--wconv" in sys.argv or "--wconv-model" in sys.argv:
         main_wconv("--wconv-model" in sys.argv)
