@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "conv_host.h"
+#include "dconv_fwd_v3_addr.h"
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
@@ -89,7 +90,7 @@ void dconv_fwd_kernel(const bf16* __restrict__ X, const float* __restrict__ W,
 }
 
 // ---------------------------------------------------------------------------
-// fwd v2 (default for the workloads' C in {1,3}): the same fp32 arithmetic
+// fwd v2 (C in {1,3}; small launches, and the A/B partner of v3): the same fp32 arithmetic
 // on the fp32 matrix unit.  v_mfma_f32_16x16x4_f32 runs at the VALU's peak
 // rate and is bit for bit a k-ordered fmaf chain on the accumulator, so
 //   acc = bias[f]; acc = fmaf(float(x), w_fp32, acc) over ky, kx, c
@@ -233,6 +234,176 @@ void dconv_fwd_v2_kernel(const bf16* __restrict__ X, const float* __restrict__ W
 }
 
 // ---------------------------------------------------------------------------
+// fwd v3 (default for C in {1,3} in large launches, see the launcher):
+// dconv_fwd_v2_kernel's arithmetic and
+// weights-in-registers layout; x arrives through LDS.  A block walks chunks
+// of R output lines (dconv_fwd_v3_addr.h).  The chunk's rows of the
+// zero-padded images are staged once, halo written as zeros, so the tile
+// loop's window reads are unpredicated ds_read_u16 counted in lgkmcnt and
+// its vector memory counter covers stores only: no tile waits for its
+// predecessor's stores.  The next chunk's rows are loaded to registers at the
+// top of a chunk and written to the other LDS buffer right after the wave's
+// first tile, in straight-line code, so the wait for them sits behind a run
+// of MFMAs and ahead of (never behind) that tile's stores in the in-order
+// counter.  One barrier per chunk.
+// ---------------------------------------------------------------------------
+template <int FT, int CT>
+__global__ __launch_bounds__(256)
+void dconv_fwd_v3_kernel(const bf16* __restrict__ X, const float* __restrict__ W,
+                         const float* __restrict__ bias, bf16* __restrict__ Y,
+                         const dfv3::Geom g) {
+  constexpr int K = 9 * CT;
+  constexpr int KS = (K + 3) / 4;    // MFMA k-steps
+  constexpr int NT = FT / 16;        // 16-channel tiles
+  __shared__ unsigned short xs[2][dfv3::kCap];
+  const int t = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
+  const int lane = tid % WAVE;
+  const int li = lane & 15;          // A: channel in tile; B, D: position in tile
+  const int g4 = lane >> 4;          // A, B: k in step; D: 4-channel group
+  const int Mtot = g.NL * g.Wo;
+
+  const float* Wt = W + (long)t * FT * CT * 9;
+  const unsigned short* Xt =
+      (const unsigned short*)X + (long)t * g.NB * g.H * g.W * CT;
+  short* Yt = (short*)Y + (long)t * Mtot * FT;
+
+  // per-lane k decode (once): weight registers, LDS tap offsets.  k padding:
+  // w = 0, and the x read (offset 0: a staged slot) is masked to 0 below
+  float wa[KS][NT];
+  int koff[KS];
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    const int k = 4 * s + g4;
+    const bool kv = k < K;
+    const int tap = kv ? k / CT : 0;
+    const int c = kv ? k - tap * CT : 0;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+      wa[s][nt] = kv ? Wt[((nt * 16 + li) * CT + c) * 9 + tap] : 0.f;
+    koff[s] = kv ? dfv3::k_off(g, k) : 0;
+  }
+  const unsigned kmask = (4 * (KS - 1) + g4 < K) ? 0xffffffffu : 0u;
+  f32x4 bv[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      bv[nt][j] = bias ? bias[(long)t * FT + nt * 16 + g4 * 4 + j] : 0.f;
+
+  // this lane's first position of a chunk: line and column (one division)
+  const int q0 = wave * dfv3::kTile + li;
+  const int l_q = q0 / g.Wo;
+  const int wo_q = q0 - l_q * g.Wo;
+
+  // chunk walk (wave-uniform): first line (img0, ho0), stride per iteration
+  int ck = blockIdx.x;
+  dfv3::Chunk ch = dfv3::chunk_at(g, ck);
+  const int dL = gridDim.x * g.R;
+  const int sdimg = dL / g.Ho, sdho = dL - sdimg * g.Ho;
+
+  // staging: slot j*256 + tid.  Branch-free: every load is issued (a zero
+  // slot reads element 0 of the task's x and is written as 0)
+  unsigned short xr[dfv3::kNLD];
+  unsigned okm;
+#define DFWD3_LOAD(IMG0, HO0)                                                  \
+  do {                                                                         \
+    okm = 0;                                                                   \
+    _Pragma("unroll")                                                          \
+    for (int j = 0; j < dfv3::kNLD; ++j) {                                     \
+      const int off = dfv3::slot_src(g, IMG0, HO0, j * dfv3::kThreads + tid);  \
+      okm |= (off >= 0 ? 1u : 0u) << j;                                        \
+      xr[j] = Xt[off >= 0 ? off : 0];                                          \
+    }                                                                          \
+  } while (0)
+#define DFWD3_WRITE(BUF)                                                       \
+  do {                                                                         \
+    _Pragma("unroll")                                                          \
+    for (int j = 0; j < dfv3::kNLD; ++j)                                       \
+      xs[BUF][j * dfv3::kThreads + tid] =                                      \
+          (okm >> j) & 1 ? xr[j] : (unsigned short)0;                          \
+  } while (0)
+
+  // one 16-position tile at lane position p / chunk position q
+#define DFWD3_TILE(FULL)                                                       \
+  do {                                                                         \
+    const bool mv = (FULL) || q < npos;                                        \
+    const int ab = mv ? p.ab : 0;                                              \
+    float xb[KS];                                                              \
+    _Pragma("unroll")                                                          \
+    for (int s = 0; s < KS; ++s)                                               \
+      xb[s] = __uint_as_float((unsigned)xc[ab + koff[s]] << 16);               \
+    xb[KS - 1] = __uint_as_float(__float_as_uint(xb[KS - 1]) & kmask);         \
+    f32x4 acc[NT];                                                             \
+    _Pragma("unroll")                                                          \
+    for (int nt = 0; nt < NT; ++nt) acc[nt] = bv[nt];                          \
+    _Pragma("unroll")                                                          \
+    for (int s = 0; s < KS; ++s)                                               \
+      _Pragma("unroll")                                                        \
+      for (int nt = 0; nt < NT; ++nt)                                          \
+        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[s][nt], xb[s],       \
+                                                       acc[nt], 0, 0, 0);      \
+    if (mv) {                                                                  \
+      _Pragma("unroll")                                                        \
+      for (int nt = 0; nt < NT; ++nt) {                                        \
+        bf16x4 v;                                                              \
+        _Pragma("unroll")                                                      \
+        for (int j = 0; j < 4; ++j)                                            \
+          v[j] = (short)__bfloat16_as_short(__float2bfloat16(acc[nt][j]));     \
+        *(bf16x4*)&Yt[(long)(m0 + q) * FT + nt * 16 + g4 * 4] = v;             \
+      }                                                                        \
+    }                                                                          \
+  } while (0)
+
+  if (ck < g.nchunks) {
+    DFWD3_LOAD(ch.img0, ch.ho0);
+    DFWD3_WRITE(0);
+  }
+  __syncthreads();
+  for (int it = 0; ck < g.nchunks; ++it) {
+    const int buf = it & 1;
+    const unsigned short* xc = xs[buf];
+    const int nlines = min(g.R, g.NL - ch.L0);
+    const int npos = nlines * g.Wo;
+    const int m0 = ch.L0 * g.Wo;
+    // next chunk of this block; past the last one every slot is a zero
+    const int nck = ck + gridDim.x;
+    int nho0 = ch.ho0 + sdho, nimg0 = ch.img0 + sdimg;
+    if (nho0 >= g.Ho) { nho0 -= g.Ho; nimg0 += 1; }
+    DFWD3_LOAD(nck < g.nchunks ? nimg0 : g.NB, nho0);
+
+    dfv3::LanePos p = dfv3::lane_init(g, ch.ho0, l_q, wo_q);
+    int q = q0;
+    int tq = wave * dfv3::kTile;     // wave-uniform tile start
+    if (tq + dfv3::kTile <= npos) {
+      DFWD3_TILE(true);
+      // the staged registers are first touched here, after the tile's
+      // stores were issued: keeps the compiler from sharing the write-out
+      // with the other branch and hoisting it (and its wait) above the tile
+      _Pragma("unroll")
+      for (int j = 0; j < dfv3::kNLD; ++j)
+        asm volatile("" : "+v"(xr[j]) : : "memory");
+      DFWD3_WRITE(buf ^ 1);
+    } else {
+      DFWD3_WRITE(buf ^ 1);
+      if (tq < npos) DFWD3_TILE(false);
+    }
+    for (tq += dfv3::kStep; tq < npos; tq += dfv3::kStep) {
+      q += dfv3::kStep;
+      dfv3::lane_advance(g, p);
+      DFWD3_TILE(false);
+    }
+    __syncthreads();
+    ck = nck;
+    ch.L0 += dL; ch.img0 = nimg0; ch.ho0 = nho0;
+  }
+#undef DFWD3_TILE
+#undef DFWD3_WRITE
+#undef DFWD3_LOAD
+}
+
+// ---------------------------------------------------------------------------
 // wgrad: dWacc [T, nsl, 9C, F] (+ dBacc [T, nsl, F]) — same accumulator
 // layout as the GEMM wgrad so the shared finalize kernel applies.
 // lane = f; wave walks contiguous positions; CT = compile-time C.
@@ -358,7 +529,7 @@ torch::Tensor dconv_fwd(torch::Tensor x, torch::Tensor w,
   }
   const long Mtot = (long)NB * Ho * Wo;
   auto stream = at::cuda::getCurrentCUDAStream();
-  // v2 (fp32 MFMA, weights in registers) for the workloads' C in {1, 3};
+  // fp32 MFMA, weights in registers (v3, v2) for the workloads' C in {1, 3};
   // MAML355_DCONV_FWD_V2=0 restores dconv_fwd_kernel everywhere
   const char* v2_env = getenv("MAML355_DCONV_FWD_V2");
   const bool v2 = (C == 1 || C == 3) && !(v2_env && v2_env[0] == '0');
@@ -369,6 +540,49 @@ torch::Tensor dconv_fwd(torch::Tensor x, torch::Tensor w,
     // positions and element offsets within a task are 32-bit in the kernel
     TORCH_CHECK(Mtot < (1L << 30) && (long)NB * H * W * C < (1L << 30),
                 "dconv_fwd: task too large for 32-bit offsets");
+    // v3 (x staged in LDS) wherever three staged rows fit its LDS buffer and
+    // the launch has at least 2^22 output positions: measured faster than v2
+    // from 4.5M positions up (128 tasks x 5 images of 84x84), slower at 2.5M
+    // and 1.1M, where a block gets one or two chunks and nothing to overlap.
+    // MAML355_DCONV_FWD_V3=0 restores dconv_fwd_v2_kernel everywhere, =1
+    // runs v3 at every size it fits
+    const char* v3_env = getenv("MAML355_DCONV_FWD_V3");
+    const bool v3_off = v3_env && v3_env[0] == '0';
+    const bool v3_forced = v3_env && v3_env[0] == '1';
+    const int fill = (2048 + T - 1) / T;   // blocks per task that fill the chip
+    const dfv3::Geom g3 = dfv3::make_geom(NB, H, W, C, (int)pad, fill);
+    // the multiply-high divisions are exact for n * d <= 2^32
+    const bool v3 = !v3_off && g3.R > 0 &&
+                    (v3_forced || (long)T * Mtot >= (1L << 22)) &&
+                    (long)(g3.Ho + dfv3::kCap) * std::max(g3.Hp, g3.RS) <
+                        (1L << 32);
+    if (v3) {
+      // ~12 chunks per block (weights and the pipeline fill amortised), but
+      // at least ~2048 blocks over the tasks where the chunks allow it
+      const long per_task = std::max<long>((g3.nchunks + 11) / 12, fill);
+      int blocks3 = (int)std::min<long>(g3.nchunks, per_task);
+      // MAML355_DCONV_FWD_V3_BLOCKS caps the blocks per task (tuning, and
+      // tests that want many chunks per block at a small shape)
+      if (const char* cap = getenv("MAML355_DCONV_FWD_V3_BLOCKS"))
+        blocks3 = std::max(1, std::min(blocks3, atoi(cap)));
+#define LAUNCH_DFWD3(FT, CT)                                                   \
+  hipLaunchKernelGGL((dconv_fwd_v3_kernel<FT, CT>), dim3(blocks3, T),          \
+                     dim3(dfv3::kThreads), 0, stream.stream(),                 \
+                     reinterpret_cast<const bf16*>(x.data_ptr()),              \
+                     wc.data_ptr<float>(), bptr,                               \
+                     reinterpret_cast<bf16*>(y.data_ptr()), g3)
+#define LAUNCH_DFWD3_C(FT)                                                     \
+  do { if (C == 1) LAUNCH_DFWD3(FT, 1); else LAUNCH_DFWD3(FT, 3); } while (0)
+      switch (F) {
+        case 16: LAUNCH_DFWD3_C(16); break;
+        case 32: LAUNCH_DFWD3_C(32); break;
+        case 48: LAUNCH_DFWD3_C(48); break;
+        default: LAUNCH_DFWD3_C(64); break;
+      }
+#undef LAUNCH_DFWD3_C
+#undef LAUNCH_DFWD3
+      return y;
+    }
     // 4 waves per block, ~8 tiles of 16 positions per wave: the per-wave
     // weight load (9C/4 * F/16 registers) is amortised, the grid stays wide
     const long ntiles = (Mtot + 15) / 16;

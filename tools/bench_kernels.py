@@ -193,27 +193,42 @@ def bench_conv_input(T, NB, H, W, C, tag):
 
 
 def bench_dconv_fwd(T, NB, H, W, C, F, tag):
-    """First-layer forward: vector-unit kernel (MAML355_DCONV_FWD_V2=0)
-    against the fp32-MFMA kernel, with the store floor (Y bytes at the HBM
-    rate) and the FMA floor (flops at the fp32 peak) beside them."""
+    """First-layer forward: vector-unit kernel (MAML355_DCONV_FWD_V2=0), the
+    fp32-MFMA kernel with per-lane loads (MAML355_DCONV_FWD_V3=0) and the
+    LDS-staged fp32-MFMA kernel (MAML355_DCONV_FWD_V3=1; the default from
+    2^22 output positions up), interleaved in one process, with
+    the spread of the rounds, the store floor (Y bytes at the HBM rate) and
+    the FMA floor (flops at the fp32 peak) beside them."""
     dev = torch.device("cuda")
     ext = hip_ext()
     x = torch.randn(T, NB, H, W, C, device=dev).to(torch.bfloat16)
     w = torch.randn(T, F, C, 3, 3, device=dev).mul(0.1)
     b = torch.randn(T, F, device=dev)
     call = lambda: ext.dconv_fwd(x, w, b, 1, H, W)  # noqa: E731
-    off = _with_env("MAML355_DCONV_FWD_V2", "0", call)
-    on = _with_env("MAML355_DCONV_FWD_V2", None, call)
-    same = torch.equal(off(), on())
-    t0, t1 = _median_rounds([off, on], rounds=3, reps=_reps_for(on), warmup=2)
+    v1 = _with_env("MAML355_DCONV_FWD_V2", "0", call)
+    v2 = _with_env("MAML355_DCONV_FWD_V3", "0", call)
+    v3 = _with_env("MAML355_DCONV_FWD_V3", "1", call)
+    y1, y2, y3 = v1(), v2(), v3()
+    same = torch.equal(y1, y3) and torch.equal(y2.view(torch.int16),
+                                               y3.view(torch.int16))
+    del y1, y2, y3
+    fns = [v1, v2, v3]
+    reps = _reps_for(v3)
+    rounds = [[timeit(f, reps=reps, warmup=2) for f in fns] for _ in range(5)]
+    med = [sorted(r[i] for r in rounds)[2] for i in range(3)]
+    spread = [max(r[i] for r in rounds) - min(r[i] for r in rounds)
+              for i in range(3)]
+    t0, t1, t2 = med
     flops = 2.0 * T * NB * H * W * F * 9 * C
     st_floor = T * NB * H * W * F * 2 / HBM_BPS
     fma_floor = flops / PEAK_F32
     print(f"[dconv-fwd {tag}] T{T} NB{NB} {H}x{W} C{C}->F{F} | "
-          f"old {t0*1e6:8.1f}us {flops/t0/1e12:5.1f}TF | "
-          f"new {t1*1e6:8.1f}us {flops/t1/1e12:5.1f}TF x{t0/t1:4.2f} | "
+          f"v1 {t0*1e6:8.1f}us | "
+          f"v2 {t1*1e6:8.1f}us +-{spread[1]*1e6:5.1f} {flops/t1/1e12:5.1f}TF | "
+          f"v3 {t2*1e6:8.1f}us +-{spread[2]*1e6:5.1f} {flops/t2/1e12:5.1f}TF "
+          f"x{t1/t2:4.2f} of v2 | "
           f"store floor {st_floor*1e6:7.1f}us FMA floor {fma_floor*1e6:7.1f}us "
-          f"(new/max floor x{t1/max(st_floor, fma_floor):4.2f}) | "
+          f"(v3/max floor x{t2/max(st_floor, fma_floor):4.2f}) | "
           f"{'equal' if same else 'DIFFERENT'}", flush=True)
     del x, w
     torch.cuda.empty_cache()
