@@ -81,7 +81,7 @@ def prepare_conv_input(x, num_filters, stride=1):
     """The first conv layer's input prepared once for every pass that reads
     the same images: x [T, NS, C, H, W] -> (nhwc, xpad), or None where the
     layer does not run on the kernels that read them (CPU, kernels disabled,
-    fp32, stride 2, C not in {1, 3}, MAML355_INPUT_PREP=0)."""
+    fp32, stride 2 up to 64 filters, C not in {1, 3}, MAML355_INPUT_PREP=0)."""
     if x.is_cuda and _want_hip(x):
         from . import hip_autograd
         return hip_autograd.prepare_conv_input(x, num_filters, stride)

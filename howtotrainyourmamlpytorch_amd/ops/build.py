@@ -35,6 +35,7 @@ SOURCES = [
     os.path.join(HIP_DIR, "wconv.hip"),
     os.path.join(HIP_DIR, "wfconv.hip"),
     os.path.join(HIP_DIR, "swconv.hip"),
+    os.path.join(HIP_DIR, "wdconv.hip"),
 ]
 
 

@@ -121,6 +121,12 @@ torch::Tensor swconv_dgrad(torch::Tensor dy, torch::Tensor wp, long pad,
                            long H, long W);
 std::vector<torch::Tensor> swconv_wgrad(torch::Tensor dy, torch::Tensor x,
                                         long pad, bool with_bias);
+// wdconv.hip
+torch::Tensor wdconv_repack(torch::Tensor w);
+bool wdconv_fits(long H, long W, long C, long pad, long stride);
+torch::Tensor wdconv_fwd(torch::Tensor x, torch::Tensor wp,
+                         c10::optional<torch::Tensor> bias, long F, long pad,
+                         long stride);
 // wfconv.hip (weights repacked by fconv_repack)
 torch::Tensor wfconv_mm(torch::Tensor x, torch::Tensor wp,
                         c10::optional<torch::Tensor> bias, long pad,
@@ -210,6 +216,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "wide-channel stride-2 3x3 conv input-grad (four parity sub-GEMMs)");
   m.def("swconv_wgrad", &swconv_wgrad,
         "wide-channel stride-2 3x3 conv weight/bias grads (ordered split-K)");
+  m.def("wdconv_repack", &wdconv_repack,
+        "repack first-layer weights as [T, 64*ceil(F/64), 32] bf16 k-rows");
+  m.def("wdconv_fits", &wdconv_fits,
+        "whether wdconv_fwd's staged rows of an H x W x C image fit its LDS");
+  m.def("wdconv_fwd", &wdconv_fwd,
+        "wide first-layer bf16 3x3 conv fwd, C in {1,3}, 65..256 filters, "
+        "stride 1 or 2, one MFMA K-step");
   m.def("wfconv_mm", &wfconv_mm,
         "task-batched fp32 MFMA 3x3 conv fwd/dgrad, 65..256 channels");
   m.def("wfconv_wgrad", &wfconv_wgrad,

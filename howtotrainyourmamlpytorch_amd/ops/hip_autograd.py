@@ -54,6 +54,14 @@ sub-GEMMs in one launch for dgrad, ordered split-K wgrad.  Bitwise
 repeatable in every mode.  ``MAML355_SWCONV=0`` restores the grouped-ATen
 composition for A/B runs.
 
+The first layer of those wide backbones (a bf16 image with C in {1, 3} and
+no gradient, 8-aligned F in 65..256, stride 1 or 2) takes the wdconv.hip
+backend: the C-channel image as stored, the whole K = 9C reduction in one
+MFMA K-step, x staged through LDS, whole-line stores; its wgrad is the wide
+trio's on the 8-channel ``xpad``.  ``MAML355_WDCONV=0`` restores the route
+through a zero-pad of x and w to 8 channels for A/B runs; an image that
+requires grad always takes that route.
+
 Convs with a stride other than 1 or 2, more than 256 channels, more than 64
 bf16 channels that are not 8-aligned, or fp32 compute at stride 2 fall back
 to the grouped-ATen composition, with a warning.
@@ -625,19 +633,33 @@ def _input_prep_on() -> bool:
 
 class PreparedInput(collections.namedtuple("PreparedInput", "nhwc xpad")):
     """The first conv layer's input as its kernels read it: ``nhwc``
-    [T, NS, H, W, C] for dconv_fwd, ``xpad`` [T, NS, H, W, 8] (zero-padded
-    channels) for tconv_wgrad_v3.  Both bf16, without a gradient."""
+    [T, NS, H, W, C] for dconv_fwd / wdconv_fwd, ``xpad`` [T, NS, H, W, 8]
+    (zero-padded channels) for tconv_wgrad_v3 / the wide wgrad kernels.  Both
+    bf16, without a gradient."""
 
 
 def prepare_conv_input(x, num_filters, stride=1):
     """x [T, NS, C, H, W] images -> PreparedInput in one pass, or None where
-    the first layer does not run on dconv_fwd + tconv_wgrad_v3 (then the
-    layer prepares its input itself, as before)."""
+    the first layer runs neither on dconv_fwd + tconv_wgrad_v3 (stride 1, up
+    to 64 filters) nor on wdconv_fwd + the wide wgrad (8-aligned 65..256
+    filters, stride 1 and 2); then the layer prepares its input itself."""
     C = x.shape[2]
-    if not (x.dtype == torch.bfloat16 and not x.requires_grad and stride == 1
-            and C in (1, 3) and x.numel() > 0 and _input_prep_on()
-            and _dconv_ok(C, num_filters) and _wgrad_v3_ok(C, num_filters)
-            and os.environ.get("MAML355_DCONV_WGRAD", "0") != "1"):
+    if not (x.dtype == torch.bfloat16 and not x.requires_grad
+            and C in (1, 3) and x.numel() > 0 and _input_prep_on()):
+        return None
+    narrow = (stride == 1 and _dconv_ok(C, num_filters)
+              and _wgrad_v3_ok(C, num_filters)
+              and os.environ.get("MAML355_DCONV_WGRAD", "0") != "1")
+    # the wide backbones' first layer (wdconv.hip fwd on nhwc, the wide
+    # trio's wgrad on xpad), at stride 1 and stride 2
+    wide = (stride in (1, 2) and num_filters % 8 == 0
+            and 64 < num_filters <= 256
+            and os.environ.get("MAML355_WDCONV", "1") != "0"
+            and os.environ.get("MAML355_WCONV" if stride == 1
+                               else "MAML355_SWCONV", "1") != "0"
+            # pad 1 stages the longer rows: what fits with it fits without
+            and _ext().wdconv_fits(x.shape[3], x.shape[4], C, 1, stride))
+    if not (narrow or wide):
         return None
     return PreparedInput(*_ext().conv_input_prep(x))
 
@@ -794,6 +816,51 @@ def _swconv_wgrad(dy, x, pad, with_bias):
 _SWCONV = _ConvBackend(_swconv_fwd, _swconv_dgrad, _swconv_wgrad)
 
 
+# ---------------------------------------------------------------------------
+# backend: the wide backbones' FIRST layer, bf16 image with C in {1, 3} into
+# 65..256 filters, stride 1 and 2 — wdconv.hip.  fwd reads the C-channel
+# image as stored (one MFMA K-step, x through LDS, whole-line stores); wgrad
+# is the wide trio's ordered split-K kernel on the 8-channel xpad, dw sliced
+# back to C (the padded channels' columns are exact zeros).  The image has no
+# gradient, so there is no dgrad, and fwd + wgrad are closed under
+# differentiation.  Bitwise repeatable.
+# ---------------------------------------------------------------------------
+def _wdconv_ok(x, w, stride, padding) -> bool:
+    """The wide first-layer backend's coverage; an x that requires grad, and an
+    image so wide that three of its rows do not fit the kernel's LDS buffer
+    (past 453 columns at C = 3, stride 1), keep the pad-to-8 route.
+    MAML355_WDCONV=0 restores that route everywhere, for A/B runs."""
+    F, C = w.shape[1], w.shape[2]
+    return (x.dtype == torch.bfloat16 and not x.requires_grad
+            and stride in (1, 2) and padding in (0, 1) and C in (1, 3)
+            and x.shape[4] == C and F % 8 == 0 and 64 < F <= 256
+            and os.environ.get("MAML355_WDCONV", "1") != "0"
+            and _ext().wdconv_fits(x.shape[2], x.shape[3], C, padding, stride))
+
+
+def _wdconv_backend(stride):
+    wide_wgrad = "wconv_wgrad" if stride == 1 else "swconv_wgrad"
+
+    def fwd(x, w, b, pad, want_stats):
+        wp = _ext().wdconv_repack(w)
+        return _ext().wdconv_fwd(x, wp, b, w.shape[1], pad, stride), None
+
+    def dgrad(dy, w, pad, H, W):
+        raise RuntimeError("maml355: the wide first-layer backend has no "
+                           "dgrad (its image carries no gradient)")
+
+    def wgrad(dy, x, pad, with_bias, xpad=None):
+        if xpad is None:
+            xpad = _ext().tconv_chpad8(x)
+        dw, db = getattr(_ext(), wide_wgrad)(dy, xpad, pad, with_bias)
+        return dw[:, :, :x.shape[4]].contiguous(), db
+
+    return _ConvBackend(fwd, dgrad, wgrad)
+
+
+_WDCONV = {1: _wdconv_backend(1), 2: _wdconv_backend(2)}
+
+
 def _fp32_backend(x, w, stride, padding):
     """The fp32 stride-1 backend for a conv — fconv.hip up to 64 channels,
     wfconv.hip for max(C, F) in 65..256 — or None where fp32 falls back."""
@@ -824,8 +891,9 @@ def _warn_fallback(reason: str) -> None:
 def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False,
                  xpad=None):
     # w is task-batched [T, F, C, 3, 3]: dim 1 = out-channels, dim 2 = in
-    # xpad: PreparedInput.xpad of x, only ever given for the bf16 stride-1
-    # first layer (prepare_conv_input returns None for everything else)
+    # xpad: PreparedInput.xpad of x, only ever given for a bf16 first layer
+    # that prepare_conv_input covers: stride 1 up to 64 filters, and the wide
+    # first layer at stride 1 and 2 (it returns None for everything else)
     fp32_be = _fp32_backend(x, w, stride, padding)
     if fp32_be is not None:
         # fp32 activations: the fp32 MFMA trio, weights and bias unrounded.
@@ -856,6 +924,18 @@ def task_conv3x3(x, w, b=None, stride=1, padding=1, return_stats=False,
         y = ref.task_conv3x3(x, wc, bc, stride, padding)
         return (y, None) if return_stats else y
     C, F = w.shape[2], w.shape[1]
+    if (wide or swide) and _wdconv_ok(x, w, stride, padding):
+        # the wide backbones' first layer: the C-channel image as stored, no
+        # pad of x or w; xpad (if prepared) feeds the wgrad
+        y = _ConvFwdFn.apply(_WDCONV[stride], x.contiguous(),
+                             w.float().contiguous(),
+                             b.float().contiguous() if b is not None else None,
+                             padding, False, xpad)[0]
+        if not return_stats:
+            return y
+        if stride == 2:
+            return y, None
+        return y, torch.empty(0, device=x.device, dtype=torch.float32)
     if stride == 2:
         # max_pooling=False backbone: the stride-2 MFMA trio.  First-layer
         # C in {1,3} is zero-padded to 8 channels (vector staging), as for

@@ -12,6 +12,8 @@
     python tools/bench_kernels.py --bn-pool-dbwd    # support BN+pool bwd / dbwd A/B
     python tools/bench_kernels.py --wconv           # wide bf16 conv trio vs grouped ATen
     python tools/bench_kernels.py --wconv-model     # 96 / 128 filters, whole-model A/B
+    python tools/bench_kernels.py --wdconv          # wide first-layer fwd vs the pad-to-8 route
+    python tools/bench_kernels.py --wdconv-model    # 96 / 128 filters, first-layer A/B
     python tools/bench_kernels.py --wfconv          # wide fp32 conv trio vs grouped ATen
     python tools/bench_kernels.py --wfconv-model    # 96 / 128 filters, fp32 modes, A/B
     python tools/bench_kernels.py --swconv          # wide bf16 stride-2 trio vs grouped ATen
@@ -861,10 +863,12 @@ def bench_wconv(T, NB, H, W, C, F, tag, pad=1):
     torch.cuda.empty_cache()
 
 
-def bench_wconv_model(filters, tasks_per_gpu, steps=2, warmup=1, rounds=3):
+def bench_wconv_model(filters, tasks_per_gpu, steps=2, warmup=1, rounds=3,
+                      toggle="MAML355_WCONV"):
     """Whole-model second-order MSL step of the mini-imagenet workload with
-    ``--cnn_num_filters filters``: the wide kernels against MAML355_WCONV=0,
-    alternating rounds in one process."""
+    ``--cnn_num_filters filters``: the wide kernels against ``toggle``=0
+    (MAML355_WCONV: the whole trio; MAML355_WDCONV: the first layer's
+    forward and input preparation only), alternating rounds in one process."""
     import argparse
     import os
     import warnings
@@ -886,7 +890,7 @@ def bench_wconv_model(filters, tasks_per_gpu, steps=2, warmup=1, rounds=3):
     batches = [tuple(t.to(dev) for t in b) for b in stream.get_train_batches(2)]
 
     def run(old):
-        os.environ["MAML355_WCONV"] = "0" if old else "1"
+        os.environ[toggle] = "0" if old else "1"
         try:
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")   # the A/B side warns
@@ -899,7 +903,7 @@ def bench_wconv_model(filters, tasks_per_gpu, steps=2, warmup=1, rounds=3):
                 torch.cuda.synchronize()
             return (time.perf_counter() - t0) / steps
         finally:
-            os.environ.pop("MAML355_WCONV", None)
+            os.environ.pop(toggle, None)
 
     tk, to = [], []
     for _ in range(rounds):
@@ -910,7 +914,7 @@ def bench_wconv_model(filters, tasks_per_gpu, steps=2, warmup=1, rounds=3):
     ro = " ".join(f"{1/t:.3f}" for t in to)
     print(f"[wconv model {filters} filters] {tasks_per_gpu} tasks/step, 2nd "
           f"order MSL | kernels {1/mk:.3f} steps/s (rounds {rk}) | "
-          f"MAML355_WCONV=0 {1/mo:.3f} steps/s (rounds {ro}) | x{mo/mk:.2f}",
+          f"{toggle}=0 {1/mo:.3f} steps/s (rounds {ro}) | x{mo/mk:.2f}",
           flush=True)
 
 
@@ -926,6 +930,62 @@ def main_wconv(with_model):
     if with_model:
         bench_wconv_model(96, 32)
         bench_wconv_model(128, 32)
+
+
+def bench_wdconv(T, NB, HW, C, F, stride):
+    """Wide first-layer forward as the model calls it (task_conv3x3 on the
+    prepared image: wdconv_repack + wdconv_fwd) against MAML355_WDCONV=0 (NHWC
+    copy, pad of x and w to 8 channels, the wide GEMM forward).  4 interleaved
+    rounds; ms min .. max and the share of the byte floor."""
+    import os
+    from howtotrainyourmamlpytorch_amd import ops
+    dev = torch.device("cuda")
+    img = torch.randn(T, NB, C, HW, HW, device=dev).to(torch.bfloat16)
+    w = torch.randn(T, F, C, 3, 3, device=dev).mul(0.1)
+    b = torch.randn(T, F, device=dev)
+    prep = ops.prepare_conv_input(img, F, stride=stride)
+    nhwc_view = img.permute(0, 1, 3, 4, 2)
+
+    def new():
+        with torch.no_grad():
+            return ops.task_conv3x3(prep.nhwc, w, b, stride=stride, padding=1,
+                                    xpad=prep.xpad)
+
+    def old():
+        os.environ["MAML355_WDCONV"] = "0"
+        try:
+            with torch.no_grad():
+                return ops.task_conv3x3(nhwc_view, w, b, stride=stride, padding=1)
+        finally:
+            os.environ.pop("MAML355_WDCONV", None)
+
+    y = new()
+    floor = (2.0 * (y.numel() + img.numel()) + 4.0 * w.numel()) / HBM_BPS
+    reps = max(2, min(20, int(0.05 / timeit(new, reps=1, warmup=1))))
+    tn, to = [], []
+    for _ in range(4):
+        tn.append(timeit(new, reps=reps, warmup=1))
+        to.append(timeit(old, reps=max(2, reps // 4), warmup=1))
+    mn, mo = sorted(tn)[2], sorted(to)[2]
+    print(f"[wdconv] T{T} NB{NB} {HW}x{HW} C{C}->F{F} stride {stride} | new "
+          f"{min(tn)*1e3:.3f} .. {max(tn)*1e3:.3f} ms | MAML355_WDCONV=0 "
+          f"{min(to)*1e3:.3f} .. {max(to)*1e3:.3f} ms | x{mo/mn:.2f} | floor "
+          f"{floor*1e3:.3f} ms, share {100*floor/mn:.0f} %", flush=True)
+    del img, w, b, prep, y
+    torch.cuda.empty_cache()
+
+
+def main_wdconv(with_model):
+    if "--wdconv" in sys.argv:
+        for f in (96, 128, 192, 256):
+            for nb in (5, 75):
+                for stride in (1, 2):
+                    bench_wdconv(128, nb, 84, 3, f, stride)
+            for nb in (5, 100):
+                bench_wdconv(32, nb, 28, 1, f, 1)
+    if with_model:
+        bench_wconv_model(96, 32, toggle="MAML355_WDCONV")
+        bench_wconv_model(128, 32, toggle="MAML355_WDCONV")
 
 
 def bench_swconv(T, NB, H, W, C, F, tag, pad=1):
@@ -1202,6 +1262,9 @@ def main():
         return
     if "--swconv" in sys.argv or "--swconv-model" in sys.argv:
         main_swconv("--swconv-model" in sys.argv)
+        return
+    if "--wdconv" in sys.argv or "--wdconv-model" in sys.argv:
+        main_wdconv("--wdconv-model" in sys.argv)
         return
     if "--wconv" in sys.argv or "--wconv-model" in sys.argv:
         main_wconv("--wconv-model" in sys.argv)
